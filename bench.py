@@ -14,6 +14,11 @@ all-reduce at the end of the timed region.
 the headline); `--workload escape` times the escape-function driver on
 res/default.toml against the CPU restatement run one cell at a time as the reference does.
 
+A plain run sets up, warms up, times the steps and prints the line (`--dump-outputs DIR` also
+writes the tallies the timed steps left, DIR/<name>.npy). `--full` adds what takes runs of its
+own: the CPU legs with the GPU-vs-port parity and the reference-pinned spatial checks
+(`--no-cpu` / `--no-ref` drop one of them from a full run).
+
 Prints ONE JSON line on rank 0. Diagnostics go to stderr.
 """
 import argparse
@@ -37,6 +42,42 @@ WORKLOADS = ("m0", "m1", "m2", "m3", "m4", "m5", "escape")
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: array} as path/<name>.npy in float64, DUMP_BYTES in all.
+    The smallest arrays are served first and each may take an equal share of what is left; a
+    larger one is written as a fixed sample of its flattened elements (sorted indices drawn
+    without replacement by a generator seeded with DUMP_SAMPLE_SEED and the array's size, so
+    two builds sample the same elements)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BYTES // 8 - 64 * len(arrays)  # elements; the .npy headers are paid for up front
+    todo = sorted(arrays.items(), key=lambda kv: np.size(kv[1]))
+    for k, (name, a) in enumerate(todo):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if left >= 0:
+            share = left // (len(todo) - k)
+            # (ascending sizes: once one array exceeds its share, so does every later one, and
+            # they all keep this share, so arrays of one shape are sampled at the same elements)
+            left = left - a.size if a.size <= share else -1
+        if a.size > share:
+            idx = np.sort(np.random.default_rng([DUMP_SAMPLE_SEED, a.size]).choice(a.size, share, replace=False))
+            log(f"[bench] --dump-outputs: {name} holds {a.size} elements, writing a seeded sample of {share}")
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def photon_counters(counters):
+    """The photons' counters of a counter array, for --dump-outputs: an engine counter such as
+    wave_iters follows the scheduling of the waves and differs from run to run."""
+    from rsmcrt_amd import abi
+    engine = [abi.CTR[n] for n in abi.ENGINE_COUNTERS]
+    return counters[[i for i in range(abi.NCOUNTERS) if i not in engine]]
 
 
 def workload(name, grid_n):
@@ -414,7 +455,7 @@ def escape_bench(args):
         # timed call, as every other workload's warm-up steps do
         eng.escape(c, photons, source=d.source, seed=d.seed)
         t0 = time.perf_counter()
-        es, _, res = eng.escape(c, photons, source=d.source, seed=d.seed)
+        es, e_grid, res = eng.escape(c, photons, source=d.source, seed=d.seed)
         t_gpu = time.perf_counter() - t0
         lay, kap = eng.classify(pos)
         live = (lay != 0) & (kap != 0.0)
@@ -436,7 +477,11 @@ def escape_bench(args):
            "scatters_per_photon": res.counter("scatters") / (run_cells * photons),
            "deposits_per_photon": res.counter("deposits") / (run_cells * photons),
            "escape_sym_max": float(es.max()), "cpu_baseline": None}
-    if not args.no_cpu:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"escape_sym": es, "escape": e_grid, "jmean": res.jmean,
+                                         "det_bins": res.det_bins, "nscatt": res.nscatt,
+                                         "counters": photon_counters(res.counters)})
+    if args.full and not args.no_cpu:
         from oracle import pyoracle as O  # the CPU leg only
         threads = args.cpu_threads or cpu_threads()
         sample = [i for i in range(len(pos)) if live[i]][:threads]
@@ -479,8 +524,14 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu1-seconds", type=float, default=8.0, help="the 1-core CPU leg (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = this process's CPU share, <= 16")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-ref", action="store_true", help="skip the reference-pinned spatial checks")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the CPU legs (16-thread and 1-core baselines, GPU-vs-port "
+                         "parity) and the reference-pinned spatial checks; a plain run does neither")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the tallies they left (what the caller of the timed path "
+                         "holds after its last step) as DIR/<name>.npy, float64, at most 64 MiB in all")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU legs")
+    ap.add_argument("--no-ref", action="store_true", help="with --full: skip the reference-pinned spatial checks")
     ap.add_argument("--no-deposit", action="store_true", help="diagnostic: pathlength deposition off")
     ap.add_argument("--sync-fold", action="store_true", help="diagnostic: each step waits for its own fold")
     ap.add_argument("--overlap", type=int, default=1, choices=(0, 1),
@@ -637,6 +688,15 @@ def main():
         timing_src = "FALLBACK: wall time per step (the event timing returned no launches)"
     cdelta = (counters - c0).cpu().numpy()  # all ranks, timed steps only
     photons = world * args.steps * B
+    if rank == 0 and args.dump_outputs:
+        # the device tallies as the last timed step (and, for N > 1, the reduce) left them: the
+        # sums over the warmup and timed steps, which the same arguments reproduce
+        arrays = {"jmean": jmean, "absorb": absorb, "nscatt": nscatt, "counters": counters}
+        if dets:
+            arrays["det_bins"] = det_bins
+        arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+        arrays["counters"] = photon_counters(arrays["counters"])
+        dump_outputs(args.dump_outputs, arrays)
 
     out = None
     if rank == 0:
@@ -708,7 +768,7 @@ def main():
         }
         if rows is not None:
             attach_rank_breakdown(out, rows)
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         threads = args.cpu_threads or cpu_threads()
         chunk = max(50, min(2000, B // 1000))
         if rank == 0:
@@ -735,7 +795,7 @@ def main():
                 out["cpu_baseline_1core"] = one
                 out["gpu_over_cpu_1core"] = out["value"] / one["value"]
             out["gpu_over_cpu"] = out["value"] / base["value"]
-    if rank == 0 and not args.no_ref:
+    if rank == 0 and args.full and not args.no_ref:
         log("[bench] reference-pinned spatial checks (validation2/3 absorb depth, fibre efficiency)")
         out.setdefault("parity", {})["reference_pinned"] = reference_pinned(torch.cuda.current_device())
     if rank == 0:

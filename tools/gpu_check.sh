@@ -11,6 +11,7 @@ timeout -k 10 ${TEST_T:-600} python -u -m pytest tests -m gpu -x -v --timeout 12
 rc=$?; echo "pytest rc=$rc"; tail -15 gpurun_out/pytest_gpu.log
 if fatal $rc || grep -q "DEVICE_FAULT\|illegal memory" gpurun_out/pytest_gpu.log; then exit 1; fi
 if [ -n "$NO_BENCH" ]; then exit 0; fi
+BENCH_ARGS=${BENCH_ARGS---full}  # the whole line (CPU legs, parity, reference-pinned checks) unless told otherwise
 timeout -k 10 ${BENCH_T:-400} python bench.py ${BENCH_ARGS} > gpurun_out/bench.json 2> gpurun_out/bench.err
 rc=$?; echo "bench rc=$rc"; cat gpurun_out/bench.json; tail -5 gpurun_out/bench.err
 exit $rc
