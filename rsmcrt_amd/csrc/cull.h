@@ -71,10 +71,21 @@ struct CullHost {
   double mean_list = 0.0;       // diagnostics
 };
 
+// Grid resolution and list cap (experiments; read with the scene's other knobs, sceneplan.h).
+// 512 cells per top (round 6; 64 before): M4 15.3 vs 13.5-13.7 M photons/s same box (1024 and
+// 2048 with more cells: 15.5, 15.6), M2 unchanged within its spread (profiles/r06_s7/ab_cull_rule.txt)
+struct CullKnobs {
+  double cells_per_top = 512.0;  // SMCRT_CULL_CPT
+  double max_cells = 1 << 18;    // SMCRT_CULL_MAX_CELLS
+  int32_t max_list = 64;         // SMCRT_CULL_MAX_LIST
+  int32_t k_nearest = 8;         // SMCRT_CULL_K
+  double u_frac = 1.0;           // SMCRT_CULL_UFRAC (the reach U of a cell's list is scaled by this)
+};
+
 // Build the grid for a scene (host). `grid_half` is the fluence grid's half extents; the
 // culling domain covers it and every bounded top. Returns enabled = false when culling does
 // not pay (few boundable tops).
 CullHost build_cull(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top, int32_t n_top,
-                    const double grid_half[3]);
+                    const double grid_half[3], const CullKnobs& knobs);
 
 }  // namespace smcrt

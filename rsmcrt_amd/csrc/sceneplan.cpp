@@ -1,0 +1,323 @@
+// sceneplan.cpp — the knob readers, plan_scene and the pure launch rules (sceneplan.h).
+// Host code only: no HIP runtime call, no kernel object.
+#include "sceneplan.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <string>
+
+#include "hosterr.h"
+
+namespace smcrt {
+namespace {
+
+int fail(int code, const std::string& msg) { return set_error(code, msg); }
+bool is(const char* v, const char* s) { return v && std::strcmp(v, s) == 0; }
+
+}  // namespace
+
+Knobs read_knobs() {
+  Knobs k;
+  auto num = [](const char* v, double d) { return v ? std::atof(v) : d; };
+  if (const char* cm = std::getenv("SMCRT_COOP_MIN_TOPS")) k.coop_min_tops = std::max(1, std::atoi(cm));
+  if (const char* cl = std::getenv("SMCRT_COOP_LANES")) k.coop_lanes = std::max(1, std::min(64, std::atoi(cl)));
+  k.coop_tab = !is(std::getenv("SMCRT_COOP_TAB"), "0");
+  k.cull = !is(std::getenv("SMCRT_CULL"), "0");
+  k.cull_grid.cells_per_top = num(std::getenv("SMCRT_CULL_CPT"), 512.0);
+  k.cull_grid.max_cells = num(std::getenv("SMCRT_CULL_MAX_CELLS"), 1 << 18);
+  k.cull_grid.max_list = (int32_t)num(std::getenv("SMCRT_CULL_MAX_LIST"), 64);
+  k.cull_grid.k_nearest = (int32_t)num(std::getenv("SMCRT_CULL_K"), 8);
+  k.cull_grid.u_frac = num(std::getenv("SMCRT_CULL_UFRAC"), 1.0);
+  k.cull_log = std::getenv("SMCRT_CULL_LOG") != nullptr;
+  k.far_march = !is(std::getenv("SMCRT_FAR_MARCH"), "0");
+  const char* dm = std::getenv("SMCRT_DEPOSIT");
+  k.deposit_atomic = is(dm, "atomic");
+  k.deposit_sorted = is(dm, "sorted");
+  if (const char* pc = std::getenv("SMCRT_POOL_CAP"))
+    k.pool_cap_chunks = std::max<uint64_t>(1, std::strtoull(pc, nullptr, 10) / CHUNK_RECORDS);
+  const char* fp = std::getenv("SMCRT_FOLD_PRIO");
+  k.fold_prio = !(fp && fp[0] == '0');
+  k.fused_hist = !is(std::getenv("SMCRT_FUSED_HIST"), "0");
+  const char* wsl = std::getenv("SMCRT_WS_SLOTS");
+  k.ws_two_slots = wsl && wsl[0] == '2';
+  const char* le = std::getenv("SMCRT_LEAN");
+  k.lean_mode = le ? (is(le, "0") ? 0 : 1) : -1;
+  const char* lm = std::getenv("SMCRT_DEBUG_LEAN_MARGIN");
+  k.lean_debug = is(lm, "all") ? 2u : (is(lm, "0") ? 1u : 0u);
+  k.verbose = std::getenv("SMCRT_VERBOSE") != nullptr;
+  return k;
+}
+
+LaunchKnobs read_launch_knobs() {
+  LaunchKnobs k;
+#ifdef SMCRT_DIAG
+  const char* dd = std::getenv("SMCRT_DIAG_DONE");
+  k.diag_done = dd && dd[0] == '1';
+#endif
+  if (const char* wm = std::getenv("SMCRT_WATCHDOG_MS")) k.watchdog_ms = std::strtod(wm, nullptr);
+  if (const char* cd = std::getenv("SMCRT_DEBUG_CLAIM_DELAY")) k.claim_delay = (uint32_t)std::strtoul(cd, nullptr, 10);
+  const char* de = std::getenv("SMCRT_DEBUG_DROP_EVENT");
+  k.drop_event = de && de[0] == '1';
+  return k;
+}
+
+PoolKnobs read_pool_knobs() {
+  PoolKnobs k;
+  if (const char* ns = std::getenv("SMCRT_SLOTS")) k.slots = std::max(2, std::min(MAX_SLOTS, std::atoi(ns)));
+  if (const char* dg = std::getenv("SMCRT_DEEP_SLOT_GIB")) {
+    k.deep_set = true;
+    k.deep_bytes = (uint64_t)std::strtoull(dg, nullptr, 10) << 30;
+  }
+  return k;
+}
+
+bool pool_log_knob() {
+  static const bool on = std::getenv("SMCRT_POOL_LOG") != nullptr;  // diagnostics
+  return on;
+}
+
+TopProps make_props(const smcrt_sdf_node& nd) {
+  TopProps p;
+  p.kappa = nd.mus + nd.mua;
+  if (nd.flags & SMCRT_NODE_ALBEDO_UNGUARDED) p.albedo = nd.mus / p.kappa;  // updateSpectral :198-199
+  else p.albedo = (nd.mua < 1e-9) ? 1.0 : nd.mus / p.kappa;
+  p.hgg = nd.hgg;
+  p.n = nd.n;
+  return p;
+}
+
+namespace {
+
+int validate(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top, int32_t n_top, const smcrt_grid* grid,
+             const smcrt_detector* dets, int32_t n_dets) {
+  if (!nodes || n_nodes < 1 || !top || n_top < 1 || !grid || n_dets < 0 || (n_dets > 0 && !dets))
+    return fail(SMCRT_ERR_INVALID_ARG, "bad scene arguments");
+  if (grid->nx < 1 || grid->ny < 1 || grid->nz < 1 || !(grid->xmax > 0) || !(grid->ymax > 0) ||
+      !(grid->zmax > 0))
+    return fail(SMCRT_ERR_INVALID_ARG, "grid dimensions must be positive");
+  if ((uint64_t)grid->nx * (uint64_t)grid->ny * (uint64_t)grid->nz >= (1ull << 32))
+    return fail(SMCRT_ERR_UNSUPPORTED, "grids of 2^32 or more voxels are not supported");
+  for (int32_t i = 0; i < n_nodes; ++i) {
+    const smcrt_sdf_node& nd = nodes[i];
+    if (nd.kind < SMCRT_SDF_SPHERE || nd.kind > SMCRT_SDF_DISPLACEMENT)
+      return fail(SMCRT_ERR_INVALID_ARG, "node " + std::to_string(i) + ": unknown SDF kind");
+    if (nd.kind == SMCRT_SDF_MODEL) {
+      if (nd.n_children < 1 || nd.first_child < 0 || nd.first_child + nd.n_children > n_nodes)
+        return fail(SMCRT_ERR_INVALID_ARG, "model node " + std::to_string(i) + ": bad child range");
+      if (nd.op < SMCRT_OP_UNION || nd.op > SMCRT_OP_INTERSECTION)
+        return fail(SMCRT_ERR_INVALID_ARG, "model node " + std::to_string(i) + ": bad CSG op");
+    } else if (composite_kind(nd.kind)) {  // a modifier wraps exactly one node
+      if (nd.n_children != 1 || nd.first_child < 0 || nd.first_child >= n_nodes)
+        return fail(SMCRT_ERR_INVALID_ARG, "modifier node " + std::to_string(i) + ": needs exactly one child");
+      if (nd.kind == SMCRT_SDF_DISPLACEMENT && nd.param[0] != (double)SMCRT_DISP_SINE)
+        return fail(SMCRT_ERR_INVALID_ARG, "displacement node " + std::to_string(i) + ": unknown function");
+    }
+  }
+  // models and modifiers nested at most PROG_MAX_DEPTH levels (geometry.h node_value); this
+  // also rejects a composite that contains itself
+  std::function<int(int32_t, int)> depth_ok = [&](int32_t idx, int lvl) -> int {
+    const smcrt_sdf_node& nd = nodes[idx];
+    if (!composite_kind(nd.kind)) return 1;
+    if (lvl >= PROG_MAX_DEPTH) return 0;
+    for (int32_t c = 0; c < nd.n_children; ++c)
+      if (!depth_ok(nd.first_child + c, lvl + 1)) return 0;
+    return 1;
+  };
+  for (int32_t i = 0; i < n_top; ++i)
+    if (top[i] >= 0 && top[i] < n_nodes && !depth_ok(top[i], 0))
+      return fail(SMCRT_ERR_UNSUPPORTED, "top " + std::to_string(i) + ": models/modifiers nested more than " +
+                                             std::to_string(PROG_MAX_DEPTH) + " levels deep are not supported");
+  for (int32_t i = 0; i < n_top; ++i)
+    if (top[i] < 0 || top[i] >= n_nodes) return fail(SMCRT_ERR_INVALID_ARG, "top index out of range");
+  for (int32_t i = 0; i < n_dets; ++i) {
+    if (dets[i].kind < SMCRT_DET_CIRCLE || dets[i].kind > SMCRT_DET_FIBRE || dets[i].nbins < 1)
+      return fail(SMCRT_ERR_INVALID_ARG, "bad detector " + std::to_string(i));
+  }
+  return SMCRT_OK;
+}
+
+bool translate_only(const smcrt_sdf_node& nd) {  // 3x3 part of the column-major transform is I
+  const double* t = nd.transform;
+  return t[0] == 1.0 && t[1] == 0.0 && t[2] == 0.0 && t[4] == 0.0 && t[5] == 1.0 && t[6] == 0.0 &&
+         t[8] == 0.0 && t[9] == 0.0 && t[10] == 1.0;
+}
+
+// flatten the SDF array into one evaluation program (eval_model fold order)
+void flatten(const smcrt_sdf_node* nodes, const int32_t* top, int32_t n_top, ScenePlan& p) {
+  std::vector<ProgOp>& prog = p.prog;
+  p.top_first.assign((size_t)n_top + 1, 0);
+  for (int32_t i = 0; i < n_top; ++i) {
+    const smcrt_sdf_node& nd = nodes[top[i]];
+    p.top_first[i] = (int32_t)prog.size();
+    if (!composite_kind(nd.kind)) {
+      prog.push_back(ProgOp{top[i], PROG_TOP, i + 1, 0, 0.0, translate_only(nd), 0});
+    } else if (nd.kind != SMCRT_SDF_MODEL) {  // a top-level modifier: one PROG_SUB op (geometry.h node_value)
+      prog.push_back(ProgOp{top[i], PROG_TOP | PROG_SUB, i + 1, 0, 0.0, 0, 0});
+    } else {
+      // eval_model's left fold, children in order; a child model or modifier is one PROG_SUB
+      // op (geometry.h node_value)
+      for (int32_t c = 0; c < nd.n_children; ++c) {
+        const int32_t ci = nd.first_child + c;
+        const bool sub = composite_kind(nodes[ci].kind);
+        prog.push_back(ProgOp{ci, (c == 0 ? PROG_CHILD_FIRST : PROG_CHILD) | (sub ? PROG_SUB : 0),
+                              c == nd.n_children - 1 ? i + 1 : 0, nd.op, nd.k, sub ? 0 : translate_only(nodes[ci]), 0});
+      }
+    }
+  }
+  p.n_prog = (int)prog.size();
+  p.top_first[n_top] = p.n_prog;
+  for (int32_t i = 0; i <= n_top; ++i)  // eval_sdfs_coop's table of each top's first op
+    prog.push_back(ProgOp{p.top_first[i], PROG_TOP, 0, 0, 0.0, 0, 0});
+  for (const ProgOp& op : prog) p.nested = p.nested || (op.action & PROG_SUB) != 0;
+}
+
+// The far-field march and glance (far.h) need every top 1-Lipschitz (exact-distance
+// primitives under translation-only transforms), a full EVAL that yields a certificate (the
+// cooperative LDS table or the culled EVAL) and a bound on the computed values' error: a few
+// ulps of the largest operand, taken here as 2^-44 of the scene's extent.
+void plan_far_march(const smcrt_sdf_node* nodes, const int32_t* top, int32_t n_top, const smcrt_grid* grid, bool fm,
+                    ScenePlan& p) {
+  double ext = grid->xmax + grid->ymax + grid->zmax + 1.0;
+  double scale = 0.0;
+  // A top qualifies if it is such a primitive, or (round 4) a model of qualifying children
+  // folded with union, intersection, subtraction or smooth union (min/max of 1-Lipschitz
+  // values is 1-Lipschitz, and so is the polynomial smooth minimum: its partials are 1 - h^2/2
+  // and h^2/2), at most 4 model levels deep so the fold's few roundings per level stay far
+  // below the bound. The near top of a certificate is still a lone sphere or box (far.h).
+  // m accumulates the operand magnitudes the error bound scales with.
+  std::function<bool(int32_t, int, double&)> far_ok = [&](int32_t idx, int lvl, double& m) -> bool {
+    const smcrt_sdf_node& nd = nodes[idx];
+    if (nd.kind == SMCRT_SDF_MODEL) {
+      const bool op_ok = nd.op == SMCRT_OP_UNION || nd.op == SMCRT_OP_INTERSECTION || nd.op == SMCRT_OP_SUBTRACTION ||
+                         (nd.op == SMCRT_OP_SMOOTH_UNION && nd.k > 0.0 && std::isfinite(nd.k));
+      if (lvl >= 4 || !op_ok || nd.n_children < 1) return false;
+      if (nd.op == SMCRT_OP_SMOOTH_UNION) m = std::max(m, nd.k);
+      for (int32_t c = 0; c < nd.n_children; ++c)
+        if (!far_ok(nd.first_child + c, lvl + 1, m)) return false;
+      return true;
+    }
+    const int32_t kd = nd.kind;
+    if (!translate_only(nd) || !(kd == SMCRT_SDF_SPHERE || kd == SMCRT_SDF_BOX || kd == SMCRT_SDF_TORUS ||
+                                 kd == SMCRT_SDF_SEGMENT || kd == SMCRT_SDF_CAPSULE))
+      return false;
+    double mm = std::fabs(nd.transform[3]) + std::fabs(nd.transform[7]) + std::fabs(nd.transform[11]);
+    for (int r = 0; r < 8; ++r) mm += std::fabs(nd.param[r]);
+    if (!std::isfinite(mm)) return false;
+    m = std::max(m, mm);
+    return true;
+  };
+  for (int32_t i = 0; fm && i < n_top; ++i) {
+    double m = 0.0;
+    fm = far_ok(top[i], 0, m);
+    scale = std::max(scale, m);
+  }
+  fm = fm && std::isfinite(ext);
+  if (fm) {
+    p.fm_err = std::ldexp(scale + ext, -44);
+    p.fm_step = std::ldexp(scale + ext, -48);
+  }
+}
+
+}  // namespace
+
+int plan_scene(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top, int32_t n_top, const smcrt_grid* grid,
+               const smcrt_detector* dets, int32_t n_dets, const Knobs& knobs, const PlanLimits& lim, ScenePlan* out) {
+  if (const int st = validate(nodes, n_nodes, top, n_top, grid, dets, n_dets)) return st;
+  ScenePlan& p = *out;
+  p.n_nodes = n_nodes;
+  p.n_top = n_top;
+  p.n_dets = n_dets;
+  p.grid = *grid;
+  p.h_nodes.assign(nodes, nodes + n_nodes);
+  p.h_top.assign(top, top + n_top);
+  for (int32_t i = 0; i < n_top; ++i) p.h_props.push_back(make_props(nodes[top[i]]));
+  p.h_dets.assign(dets, dets + n_dets);
+  p.h_det_off.assign((size_t)n_dets + 1, 0);
+  for (int32_t i = 0; i < n_dets; ++i) {
+    const int64_t nb = dets[i].nbins;
+    p.h_det_off[i + 1] = p.h_det_off[i] + (dets[i].kind == SMCRT_DET_CAMERA ? nb * nb : nb);
+  }
+  p.det_total = p.h_det_off[n_dets];
+  // voxel faces, grid.f90:147-157: (i-1)*2*max/n; zface has nz+2 entries
+  for (int32_t i = 0; i < grid->nx + 1; ++i) p.faces.push_back((double)i * 2.0 * grid->xmax / (double)grid->nx);
+  for (int32_t i = 0; i < grid->ny + 1; ++i) p.faces.push_back((double)i * 2.0 * grid->ymax / (double)grid->ny);
+  for (int32_t i = 0; i < grid->nz + 2; ++i) p.faces.push_back((double)i * 2.0 * grid->zmax / (double)grid->nz);
+  flatten(nodes, top, n_top, p);
+  // A sparse wave evaluates its lanes' SDF arrays one lane at a time across the wave when
+  // that is cheaper than the serial per-lane chain over all n_top tops (transport.h).
+  p.coop_lanes = n_top >= knobs.coop_min_tops ? std::max(1, std::min(16, n_top / ((n_top + 63) / 64 + 3))) : 0;
+  if (knobs.coop_lanes && p.coop_lanes > 0) p.coop_lanes = knobs.coop_lanes;
+  {  // The cooperative EVAL's LDS table: at most 64 tops, none of them a model (transport.h).
+    bool ok = p.coop_lanes > 0 && n_top <= 64 && knobs.coop_tab;
+    for (int32_t i = 0; ok && i < n_top; ++i) ok = !composite_kind(nodes[top[i]].kind);
+    if (ok) {
+      p.ctab.assign(CTAB_DOUBLES, 0.0);
+      for (int32_t i = 0; i < n_top; ++i) {
+        const smcrt_sdf_node& nd = nodes[top[i]];
+        for (int r = 0; r < 12; ++r) p.ctab[r * 64 + i] = nd.transform[r];
+        for (int r = 0; r < 8; ++r) p.ctab[(12 + r) * 64 + i] = nd.param[r];
+        p.ctab[20 * 64 + i] = (double)nd.kind + (translate_only(nd) ? 16.0 : 0.0);
+      }
+    }
+  }
+  const double maxes[3] = {grid->xmax, grid->ymax, grid->zmax};
+  // exact culling of the SDF array for many-top scenes (cull.h)
+  if (p.coop_lanes > 0 && knobs.cull) p.cull = build_cull(nodes, n_nodes, top, n_top, maxes, knobs.cull_grid);
+  if (!p.ctab.empty() || p.cull.enabled) plan_far_march(nodes, top, n_top, grid, knobs.far_march, p);
+  // n*p/(2*max) may be computed as n*p*inv exactly when 2*max is a power of two
+  for (int a = 0; a < 3; ++a) {
+    int ex = 0;
+    const double m = std::frexp(2.0 * maxes[a], &ex);
+    p.inv2[a] = (m == 0.5 && std::isfinite(1.0 / (2.0 * maxes[a]))) ? 1.0 / (2.0 * maxes[a]) : 0.0;
+  }
+  {
+    const bool p2 = p.inv2[0] != 0.0 && p.inv2[1] != 0.0 && p.inv2[2] != 0.0;
+    const int32_t ns[3] = {grid->nx, grid->ny, grid->nz};
+    bool f2 = p2;
+    for (int a = 0; a < 3; ++a) {
+      if ((ns[a] & (ns[a] - 1)) != 0) { f2 = false; continue; }
+      int e2m = 0, en = 0;  // 2*max = 2^(e2m-1), n = 2^(en-1)
+      (void)std::frexp(2.0 * maxes[a], &e2m);
+      (void)std::frexp((double)ns[a], &en);
+      p.fe[a] = e2m - en;  // face k = k * 2*max/n = k * 2^fe
+    }
+    p.grid_mode = f2 ? 2 : (p2 ? 1 : 0);
+  }
+  {  // binned deposition (deposit.h); SMCRT_DEPOSIT=sorted (or a disabled fused histogram) keeps the sorted record path
+    const uint64_t nv = (uint64_t)grid->nx * grid->ny * grid->nz;
+    const uint64_t tiles = (nv + TILE_VOXELS - 1) / TILE_VOXELS;
+    p.n_tiles = (tiles <= MAX_TILES && nv < 0xFFFFFFFFull) ? (uint32_t)tiles : 0;
+    p.force_atomic = knobs.deposit_atomic;
+    p.pool_cap_chunks = knobs.pool_cap_chunks;
+    const bool sorted = knobs.deposit_sorted || !knobs.fused_hist;
+    p.bucketed = !sorted && p.n_tiles > 0 && p.n_tiles <= MAX_DIRECT_TILES;
+    p.hist_tiles = (!p.bucketed && knobs.fused_hist && p.n_tiles > 0 && p.n_tiles <= MAX_FUSED_HIST_TILES) ? p.n_tiles : 0;
+  }
+  p.face_bytes = p.faces.size() * sizeof(double) + sizeof(TopProps) * (size_t)n_top;
+  p.lds_faces = p.face_bytes <= MAX_FACE_BYTES;
+  for (int32_t i = 1; i < n_top; ++i) p.fresnel = p.fresnel || p.h_props[i].n != p.h_props[0].n;
+  {  // the lean path (ws.h): scenes with a few tops
+    bool ok = p.bucketed && p.coop_lanes == 0 && grid->nx < (1 << 20) - 2 && grid->ny < (1 << 20) - 2 &&
+              grid->nz < (1 << 20) - 2;
+    // three segment slots per photon when their LDS fits beside the tile words and faces, else
+    // two (SMCRT_WS_SLOTS=2 forces two)
+    p.ws_slots = (!knobs.ws_two_slots && lean_lds(p) + lim.ws_shared3 <= LDS_BYTES) ? 3 : 2;
+    ok = ok && lean_lds(p) + (p.ws_slots == 3 ? lim.ws_shared3 : lim.ws_shared2) <= LDS_BYTES;
+    p.lean_mode = knobs.lean_mode;
+    // Scenes with detectors take the lean path only when forced (SMCRT_LEAN=1): record_hits at
+    // every segment end keeps their photon waves the bottleneck, and transport_kernel measured
+    // faster on M5 (43.0 vs 30.3-31.1 M photons/s). Fresnel scenes take it (reflect_refract runs
+    // in the event waves): M3 169.2-169.8 vs 144.0-144.3 (profiles/r05_ws/ab_m3_m5_fresnel_events.txt)
+    p.lean_candidate = ok && !p.nested && (p.lean_mode == 1 || (p.lean_mode != 0 && n_dets == 0));
+    p.lean_debug = knobs.lean_debug;
+  }
+  p.fold_prio = knobs.fold_prio;
+  p.cull_log = knobs.cull_log;
+  p.verbose = knobs.verbose;
+  return SMCRT_OK;
+}
+
+}  // namespace smcrt

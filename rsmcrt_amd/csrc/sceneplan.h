@@ -1,0 +1,210 @@
+// sceneplan.h — the engine's host policy without a device: the SMCRT_* knobs, the plan of a
+// scene (validation, the flattened SDF program, the kernel instantiation and deposition path
+// it gets) and the pure sizing rules of the record pool and of a launch.
+//
+// Nothing here makes a HIP runtime call or needs a kernel object: smcrt.hip reads the knobs,
+// calls plan_scene and then only uploads the plan and owns the device state (devmem.h);
+// tests/sceneplan_probe.cpp prints a plan on a machine without a GPU. Every value that
+// reaches a kernel (fm_err, fm_step, inv2, fe, the faces, the lean margins, the cull grid)
+// keeps the operations and their order that the kernels' bit-exact parity was measured with.
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/smcrt.h"
+#include "transport.h"  // (before deposit.h, which uses KParams)
+#include "cull.h"
+#include "deposit.h"
+
+namespace smcrt {
+
+// Record-log slots (and internal launch streams) per scene: launches whose pools are small
+// enough run up to MAX_SLOTS deep, so long-tailed launches overlap more than pairwise.
+constexpr int MAX_SLOTS = 4;
+#ifndef SMCRT_DEEP_SLOT_GIB
+#define SMCRT_DEEP_SLOT_GIB 24
+#endif
+constexpr uint64_t DEEP_SLOT_BYTES = (uint64_t)SMCRT_DEEP_SLOT_GIB << 30;  // a slot pool at most this large: MAX_SLOTS slots
+
+// The words of smcrt_scene::d_queue: a work-queue head per launch stream, then the scene's
+// running totals and the watchdog word (transport.h watchdog_expired).
+enum QueueWord : int {
+  Q_STREAM0 = 0,         // heads of the internal streams 0 .. MAX_SLOTS-1
+  Q_CALLER = MAX_SLOTS,  // head of launches on the caller's stream
+  Q_FAR_STEPS,           // far-field march steps (far.h)
+  Q_FOLD_TICKS,          // bk_reduce workgroup run time, s_memrealtime ticks
+  Q_LEAN_HAZARDS,        // deferred lean segments that ended in tflag or an error stop (lean.h)
+  Q_WATCHDOG,            // the first expired wait: site | (block + 1) << 8
+  Q_COUNT
+};
+constexpr int N_QUEUES = Q_CALLER + 1;  // launch streams: each has a queue head, a KCold ring, a lane scratch
+
+constexpr size_t LDS_BYTES = 163840;        // a workgroup's LDS ceiling (160 KiB)
+constexpr size_t MAX_FACE_BYTES = 40960;    // props + voxel faces are staged in LDS up to this size
+constexpr uint32_t MAX_FUSED_HIST_TILES = 512;  // 8 KiB of LDS per block for the wave histograms
+// Record pool: record indices in the bin kernels are 32-bit, so at most 2^32 - 2^28 records
+// (30 GiB, plus the same again for the sorted copy) per launch; a launch that would need more
+// is split into sub-batches. POOL_SLACK covers the spread of records per photon between
+// batches; a launch that still overflows folds the excess with atomics (exact, slower).
+constexpr uint64_t MAX_POOL_RECORDS = (1ull << 32) - (1ull << 28);
+constexpr double POOL_SLACK = 1.15;
+constexpr double DEFAULT_WATCHDOG_MS = 2000.0;  // a wait past 2 s of wall clock is a lost wake-up
+
+// ---- knobs: every SMCRT_* setting of smcrt.hip and cull.cpp, each read at one moment ----
+struct Knobs {  // read_knobs(): at scene creation
+  int32_t coop_min_tops = 8;  // SMCRT_COOP_MIN_TOPS: the fewest tops that get the COOP instantiation
+  int32_t coop_lanes = 0;     // SMCRT_COOP_LANES (experiments: the sparse-wave threshold); 0 = the rule
+  bool coop_tab = true;       // SMCRT_COOP_TAB=0 keeps the global-memory cooperative EVAL
+  bool cull = true;           // SMCRT_CULL=0
+  CullKnobs cull_grid;        // SMCRT_CULL_CPT / _MAX_CELLS / _MAX_LIST / _K / _UFRAC
+  bool cull_log = false;      // SMCRT_CULL_LOG
+  bool far_march = true;      // SMCRT_FAR_MARCH=0
+  bool deposit_atomic = false, deposit_sorted = false;  // SMCRT_DEPOSIT=atomic / =sorted
+  uint64_t pool_cap_chunks = 0;  // SMCRT_POOL_CAP (records; tests of pool exhaustion): 0 = none
+  bool fold_prio = true;      // SMCRT_FOLD_PRIO=0: the fold stream at normal priority
+  bool fused_hist = true;     // SMCRT_FUSED_HIST=0
+  bool ws_two_slots = false;  // SMCRT_WS_SLOTS=2
+  int lean_mode = -1;         // SMCRT_LEAN: -1 automatic, 0 off, 1 forced
+  uint32_t lean_debug = 0;    // SMCRT_DEBUG_LEAN_MARGIN (tests only): 1 = "0", 2 = "all"
+  bool verbose = false;       // SMCRT_VERBOSE
+};
+struct LaunchKnobs {  // read_launch_knobs(): at every launch
+  double watchdog_ms = DEFAULT_WATCHDOG_MS;  // SMCRT_WATCHDOG_MS; 0: unbounded waits
+  uint32_t claim_delay = 0;  // SMCRT_DEBUG_CLAIM_DELAY (tests only)
+  bool drop_event = false;   // SMCRT_DEBUG_DROP_EVENT=1 (tests only: the watchdog's proof)
+  bool diag_done = false;    // SMCRT_DIAG_DONE=1 (diagnostic builds: completion times)
+};
+struct PoolKnobs {  // read_pool_knobs(): when the record pool is (re)allocated
+  int slots = 0;            // SMCRT_SLOTS clamped to 2 .. MAX_SLOTS; 0 = the rule
+  bool deep_set = false;    // SMCRT_DEEP_SLOT_GIB given
+  uint64_t deep_bytes = 0;
+};
+Knobs read_knobs();
+LaunchKnobs read_launch_knobs();
+PoolKnobs read_pool_knobs();
+bool pool_log_knob();  // SMCRT_POOL_LOG, read once
+
+// ---- the plan ----
+struct PlanLimits {
+  size_t ws_shared2 = 0, ws_shared3 = 0;  // sizeof(WsSharedT<2>), sizeof(WsSharedT<3>): ws_kernel's static LDS
+};
+
+struct ScenePlan {
+  int n_nodes = 0, n_top = 0, n_dets = 0;
+  smcrt_grid grid{};
+  int64_t det_total = 0;
+  std::vector<smcrt_sdf_node> h_nodes;
+  std::vector<int32_t> h_top;
+  std::vector<TopProps> h_props;
+  std::vector<smcrt_detector> h_dets;
+  std::vector<int64_t> h_det_off;
+  std::vector<double> faces;  // x (nx+1) | y (ny+1) | z (nz+2)
+  // the SDF array flattened into one evaluation program (eval_model fold order), followed by
+  // eval_sdfs_coop's table of each top's first op (n_top + 1 entries after the n_prog ops)
+  std::vector<ProgOp> prog;
+  std::vector<int32_t> top_first;
+  int n_prog = 0;
+  // a top model has a model or modifier among its children, or a top is a modifier: only the
+  // general instantiation evaluates composites below the top level (geometry.h node_value), so
+  // such scenes always run it: with many tops its COOP variant (cooperative and culled EVALs,
+  // round 4), else the serial EVAL; never the lean kernel
+  bool nested = false;
+  int coop_lanes = 0;
+  std::vector<double> ctab;  // the cooperative EVAL's primitive table (transport.h), or empty
+  CullHost cull;             // exact SDF culling (cull.h): grid + lists + the always-evaluated tops
+  // far-field march (far.h): KParams::fm_err / fm_step, 0 when the scene does not qualify
+  double fm_err = 0.0, fm_step = 0.0;
+  double inv2[3] = {0.0, 0.0, 0.0};
+  int grid_mode = 0;  // transport_kernel<*, GM>: 1 = every 2*max a power of two, 2 = and every n too
+  int32_t fe[3] = {0, 0, 0};
+  uint32_t n_tiles = 0;          // binned jmean deposition (deposit.h); 0: the grid has too many tiles
+  bool force_atomic = false;     // SMCRT_DEPOSIT=atomic
+  uint64_t pool_cap_chunks = 0;  // SMCRT_POOL_CAP
+  bool bucketed = false;    // records go straight into per-tile buckets (deposit.h); else sorted path
+  uint32_t hist_tiles = 0;  // fused tile histogram in the transport kernel (0: bin_hist kernel)
+  size_t face_bytes = 0;
+  bool lds_faces = false;   // stage props + voxel faces in LDS when they fit
+  bool fresnel = false;     // two tops with different refractive indices
+  int ws_slots = 3;         // ws_kernel's segment slots per photon: 3, or 2 when 3 do not fit the LDS (ws.h)
+  // SMCRT_LEAN. (Rounds 3-4 chose lean_kernel only up to 5.5 voxel crossings per segment: long
+  // walks were cheaper in one lane. ws_kernel's walker waves take them at any length: M0, 8.2
+  // crossings per segment, 54.9 vs 43.4-44.2 M photons/s on transport_kernel,
+  // profiles/r05_ws/ab_m0.txt.)
+  int lean_mode = -1;
+  uint32_t lean_debug = 0;
+  // the lean path (ws_kernel) serves this scene: a few tops, bucketed deposition, axes below
+  // 2^20 cells, its LDS fits (SMCRT_LEAN=0 keeps transport_kernel); the lane-scratch
+  // allocation may still veto it (smcrt_scene::lean_ok)
+  bool lean_candidate = false;
+  bool fold_prio = true, cull_log = false, verbose = false;  // (knobs the device side acts on)
+};
+
+// Validate the scene and decide everything about it that needs no device. Returns SMCRT_OK,
+// or the status with its message in smcrt_last_error (hosterr.h).
+int plan_scene(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top, int32_t n_top, const smcrt_grid* grid,
+               const smcrt_detector* dets, int32_t n_dets, const Knobs& knobs, const PlanLimits& lim, ScenePlan* out);
+
+TopProps make_props(const smcrt_sdf_node& nd);  // init_mono, opticalProperties.f90:107-125
+
+// ---- pure rules of the launch path ----
+// the lean path's dynamic LDS (ws_kernel): staged props + faces, then the block's bucket words
+inline size_t lean_lds(const ScenePlan& p) {
+  return (p.lds_faces ? p.face_bytes : 0) + (size_t)2 * p.n_tiles * sizeof(uint32_t);
+}
+// 32-bit LDS words of a block's deposit state (deposit.h): a tile histogram per wave, or one
+// 64-bit bucket word per tile shared by the block.
+inline uint32_t dep_words(const ScenePlan& p) { return p.bucketed ? 2 * p.n_tiles : 4 * p.hist_tiles; }
+// Dynamic LDS of the transport kernel: staged props + faces, detector start points, then the
+// deposit words, then the coop table.
+inline size_t transport_lds(const ScenePlan& p, uint32_t dep_words, bool xsrc) {
+  const bool ctab = !p.ctab.empty() && p.coop_lanes > 0;  // the COOP instantiations stage it
+  // (the general emitter with the COOP machinery keeps its faces in device memory, kernel_ptrs.h)
+  const bool faces = p.lds_faces && !(xsrc && p.coop_lanes > 0);
+  return (faces ? p.face_bytes : 0) + (p.n_dets ? 3 * 256 * sizeof(double) : 0) +
+         (size_t)dep_words * sizeof(uint32_t) + (ctab ? CTAB_DOUBLES * sizeof(double) : 0);
+}
+// Pool records that a launch of `blocks` transport blocks does not fill: per wave, the last
+// chunk (sorted path); bucketed: per block and tile an open bucket and its pre-taken
+// successor, per wave a batch of unused ids.
+inline double pool_slack_records(const ScenePlan& p, int blocks) {
+  const double waves = (double)blocks * 4.0;
+  return p.bucketed ? (waves / 4.0 * 2.0 * p.n_tiles + waves * BUCKET_BATCH) * BUCKET_RECORDS
+                    : waves * CHUNK_RECORDS;
+}
+// Records the record pool must hold for one launch of n photons at rpp records per photon.
+inline uint64_t pool_records_for(const ScenePlan& p, int blocks, uint64_t n, double rpp) {
+  const double want = (double)n * rpp * POOL_SLACK + pool_slack_records(p, blocks);
+  return (uint64_t)std::min(want, (double)MAX_POOL_RECORDS);
+}
+// Record-log slots for pools of cap_bytes per slot: MAX_SLOTS while a slot is at most
+// DEEP_SLOT_BYTES (or 60 % of the device's total_mem over MAX_SLOTS, if more;
+// SMCRT_DEEP_SLOT_GIB overrides), larger pools two. Scenes of the lean kernel and of the
+// far-field march keep two at any size; SMCRT_SLOTS overrides that choice.
+inline int slot_depth(const PoolKnobs& k, bool lean_or_far, uint64_t cap_bytes, uint64_t total_mem) {
+  const int want = k.slots ? k.slots : (lean_or_far ? 2 : MAX_SLOTS);
+  uint64_t deep = std::max<uint64_t>(DEEP_SLOT_BYTES, (uint64_t)(0.6 * (double)total_mem) / MAX_SLOTS);
+  if (k.deep_set) deep = k.deep_bytes;
+  return cap_bytes <= deep ? want : 2;
+}
+// binned deposition needs path-length tallies into jmean with unit weights (fp32 record
+// values are exact only then) and a grid of at most MAX_TILES tiles
+inline bool launch_binned(const ScenePlan& p, bool has_jmean, uint32_t flags) {
+  return has_jmean && (flags & SMCRT_FLAG_PATHLENGTH) && !(flags & SMCRT_FLAG_SURVIVAL_BIAS) && p.n_tiles > 0 &&
+         !p.force_atomic;
+}
+// the lean path (ws_kernel, ws.h) when the scene and the run qualify: bucketed path-length
+// deposition, unit weights (no survival bias), a plain source
+inline bool launch_lean(bool lean_ok, bool xsrc, uint32_t bucket_tiles, uint32_t flags) {
+  return !xsrc && lean_ok && bucket_tiles && (flags & SMCRT_FLAG_PATHLENGTH) && !(flags & SMCRT_FLAG_SURVIVAL_BIAS);
+}
+// lean_margin per axis (lean.h, ws.h), with the operations the kernel used to do
+inline void lean_margins(uint32_t lean_debug, const smcrt_grid& g, double lo[3], double hi[3]) {
+  const double eps = 1e-8, mf = (lean_debug & 3u) ? 0.0 : 2.0 * eps;
+  const double mx = mf * (double)(g.nx + 2), my = mf * (double)(g.ny + 2), mz = mf * (double)(g.nz + 2);
+  lo[0] = mx; lo[1] = my; lo[2] = mz;
+  hi[0] = 2.0 * g.xmax - mx; hi[1] = 2.0 * g.ymax - my; hi[2] = 2.0 * g.zmax - mz;
+}
+
+}  // namespace smcrt

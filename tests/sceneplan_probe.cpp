@@ -1,0 +1,67 @@
+// sceneplan_probe.cpp — prints the engine's device-free decisions (rsmcrt_amd/csrc/sceneplan.h)
+// as key=value lines, for tests/planprobe.py. Host code only: built from this file,
+// sceneplan.cpp and cull.cpp; no kernel object, no libsmcrt.so, no GPU.
+//
+//   sceneplan_probe plan FILE   FILE: int32 n_nodes, n_top, n_dets | smcrt_sdf_node[n_nodes] |
+//                               int32 top[n_top] | smcrt_grid | smcrt_detector[n_dets]
+//   sceneplan_probe slots LEAN_OR_FAR CAP_BYTES TOTAL_MEM
+// The SMCRT_* knobs come from the environment, through the readers the library uses.
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "../rsmcrt_amd/csrc/hosterr.h"
+#include "../rsmcrt_amd/csrc/kernels.h"  // WsSharedT (ws.h, in the order it needs)
+#include "../rsmcrt_amd/csrc/sceneplan.h"
+
+thread_local std::string smcrt::g_last_error;
+using namespace smcrt;
+
+template <class T>
+static bool read_n(std::FILE* f, std::vector<T>& v, size_t n) {
+  v.resize(n);
+  return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
+}
+
+static int plan(const char* path) {
+  std::FILE* f = std::fopen(path, "rb");
+  int32_t hdr[3];
+  if (!f || std::fread(hdr, sizeof(int32_t), 3, f) != 3 || hdr[0] < 0 || hdr[1] < 0 || hdr[2] < 0) return 2;
+  std::vector<smcrt_sdf_node> nodes;
+  std::vector<int32_t> top;
+  std::vector<smcrt_grid> grid;
+  std::vector<smcrt_detector> dets;
+  if (!read_n(f, nodes, hdr[0]) || !read_n(f, top, hdr[1]) || !read_n(f, grid, 1) || !read_n(f, dets, hdr[2])) return 2;
+  std::fclose(f);
+  const PlanLimits lim{sizeof(WsSharedT<2>), sizeof(WsSharedT<3>)};
+  ScenePlan p;
+  const int st = plan_scene(nodes.data(), hdr[0], top.data(), hdr[1], grid.data(), hdr[2] ? dets.data() : nullptr, hdr[2],
+                            read_knobs(), lim, &p);
+  std::printf("status=%d\nerror=%s\n", st, g_last_error.c_str());
+  if (st) return 0;
+  std::printf("det_total=%lld\nh_det_off=", (long long)p.det_total);
+  for (int64_t o : p.h_det_off) std::printf("%lld,", (long long)o);
+  std::printf("\nn_prog=%d\nprog_size=%zu\nnested=%d\ncoop_lanes=%d\nctab=%d\ncull=%d\n", p.n_prog, p.prog.size(),
+              (int)p.nested, p.coop_lanes, (int)!p.ctab.empty(), (int)p.cull.enabled);
+  std::printf("fm_err=%a\nfm_step=%a\ninv2=%a,%a,%a\nfe=%d,%d,%d\ngrid_mode=%d\n", p.fm_err, p.fm_step, p.inv2[0],
+              p.inv2[1], p.inv2[2], p.fe[0], p.fe[1], p.fe[2], p.grid_mode);
+  std::printf("n_tiles=%u\nforce_atomic=%d\npool_cap_chunks=%llu\nbucketed=%d\nhist_tiles=%u\n", p.n_tiles,
+              (int)p.force_atomic, (unsigned long long)p.pool_cap_chunks, (int)p.bucketed, p.hist_tiles);
+  std::printf("face_bytes=%zu\nlds_faces=%d\nfresnel=%d\nws_slots=%d\nlean_mode=%d\nlean_debug=%u\nlean_candidate=%d\n",
+              p.face_bytes, (int)p.lds_faces, (int)p.fresnel, p.ws_slots, p.lean_mode, p.lean_debug, (int)p.lean_candidate);
+  std::printf("lean_lds=%zu\ntransport_lds=%zu\n", lean_lds(p), transport_lds(p, dep_words(p), false));
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  const std::string mode = argc > 1 ? argv[1] : "";
+  if (mode == "plan" && argc == 3) return plan(argv[2]);
+  if (mode == "slots" && argc == 5) {
+    std::printf("slots=%d\n", slot_depth(read_pool_knobs(), std::atoi(argv[2]) != 0, std::strtoull(argv[3], nullptr, 10),
+                                         std::strtoull(argv[4], nullptr, 10)));
+    return 0;
+  }
+  std::fprintf(stderr, "usage: sceneplan_probe plan FILE | slots LEAN_OR_FAR CAP_BYTES TOTAL_MEM\n");
+  return 2;
+}

@@ -2,7 +2,7 @@
 
 The march's certificate (far.h header) needs every computed top-level SDF value within
 fm_err of the true distance, and the rounding of each step p + d*dir within fm_step. The host
-sets both from the scene's scale (smcrt.hip scene creation, "far-field march" block):
+sets both from the scene's scale (sceneplan.cpp plan_far_march):
     ext     = xmax + ymax + zmax + 1
     scale   = max over tops of |t14| + |t24| + |t34| + sum |param[0..7]|
     fm_err  = 2^-44 (scale + ext),   fm_step = 2^-48 (scale + ext).
@@ -32,7 +32,7 @@ FAR_KINDS = (abi.SDF_SPHERE, abi.SDF_BOX, abi.SDF_TORUS, abi.SDF_SEGMENT, abi.SD
 
 
 def node_scale(sc, i):
-    """The operand magnitude a top contributes to the bound (smcrt.hip far_ok): a primitive's
+    """The operand magnitude a top contributes to the bound (sceneplan.cpp far_ok): a primitive's
     translation and parameters; a model's largest child, and its smooth-union k."""
     nd = sc.nodes[i]
     if nd.kind == abi.SDF_MODEL:
@@ -43,7 +43,8 @@ def node_scale(sc, i):
 
 
 def fm_bounds(sc, g):
-    """fm_err, fm_step as the host computes them (smcrt.hip, far-field block)."""
+    """fm_err, fm_step as the host computes them (sceneplan.cpp plan_far_march;
+    tests/test_sceneplan.py checks the two agree bit for bit)."""
     ext = g.xmax + g.ymax + g.zmax + 1.0
     scale = max(node_scale(sc, i) for i in sc.top)
     return np.ldexp(scale + ext, -44), np.ldexp(scale + ext, -48)
@@ -193,7 +194,7 @@ def exact_node(sc, i, p):
 def test_far_field_error_bound_models(scale_of):
     """Round 4: a model of far-eligible primitives folded with union, smooth union,
     subtraction or intersection (two levels deep too) qualifies for the far-field march as a
-    non-near top (smcrt.hip far_ok). Its computed value must be within the same bound:
+    non-near top (sceneplan.cpp far_ok). Its computed value must be within the same bound:
     evaluated by the restatement at adversarial points of every child, against the fold in
     60-digit decimal arithmetic."""
     from rsmcrt_amd.scene import box, capsule, model, sphere, torus

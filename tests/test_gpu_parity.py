@@ -1007,6 +1007,36 @@ def test_lean_path_two_slots_by_lds():
     compare(gpu, cpu)
 
 
+@pytest.mark.parametrize("case", ["sphere", "skin-detector", "nested"])
+def test_plan_predicts_path(case):
+    """The device-free plan (sceneplan.h, printed by tests/sceneplan_probe.cpp) says which
+    kernel a scene runs: its lean_candidate, with the run's flags (path-length deposition, no
+    survival bias, a plain source), is whether the engine launched the lean kernel; and the
+    photons are the oracle's either way."""
+    from tests import planprobe
+    from tests.test_abi import _nested
+    g, src, dets, flags = scene.grid(16, 16, 16, 1, 1, 1), scene.point_source(), [], abi.FLAG_PATHLENGTH
+    if case == "sphere":
+        sc = builders.setup_sphere(10.0, 0.1, 0.9, 1.0, 1.0)
+    elif case == "skin-detector":
+        sc, g = builders.skin_layers(), scene.grid(16, 16, 16, 0.05, 0.05, 0.05)
+        src = scene.pencil_source((0.0, 0.0, 0.0499), (0.0, 0.0, -1.0))
+        dets = [scene.circle_dect((0.0, 0.0, 0.0499), (0.0, 0.0, 1.0), 1, 0.05, 50)]
+    else:
+        sc = _nested(3)
+    plan = planprobe.plan(sc, g, dets)
+    assert plan["status"] == abi.OK
+    assert plan["lean_candidate"] == (1 if case == "sphere" else 0)  # (detectors, composites below a top: not lean)
+    want_lean = bool(plan["lean_candidate"]) and bool(flags & abi.FLAG_PATHLENGTH) and \
+        not flags & abi.FLAG_SURVIVAL_BIAS
+    with Engine(sc, g, dets) as eng:
+        eng.kernel_times()
+        gpu = eng.run(src, 2000, seed=SEED, flags=flags, records=True)
+        kt = eng.kernel_times()
+    assert (kt["lean_launches"] > 0) == want_lean, (plan, kt)
+    compare(gpu, O.run(sc, g, src, 2000, seed=SEED, flags=flags, dets=dets, records=True))
+
+
 @pytest.mark.parametrize("knob", ["0", "all"])
 def test_lean_hazards_counted_as_faults(monkeypatch, knob):
     """A deferred lean-kernel walk (lean.h) must never end in tflag or an error stop; if one
