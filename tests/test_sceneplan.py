@@ -14,7 +14,7 @@ import pytest
 
 import bench
 from rsmcrt_amd import abi, builders, scene
-from tests import planprobe
+from tests import plan_cases, planprobe
 from tests.test_abi import _nested
 from tests.test_far_bound import fm_bounds
 
@@ -119,6 +119,40 @@ def test_deposit_paths():
     # 264 * 256 * 256 voxels are 1056 tiles of 2^14: binned, but past the 1024 direct tiles
     p = planprobe.plan(sc, scene.grid(264, 256, 256, 1, 1, 1))
     assert p["n_tiles"] == 1056 and p["bucketed"] == 0 and p["lean_candidate"] == 0
+
+
+def test_plan_table_covers_every_instantiation():
+    """tests/plan_cases.py: its matrix is the 24 ws_kernel and 21 transport_kernel instantiations
+    of kinst.hip, once each, beside the five deposit-regime sizes, the six axis-bound and the
+    eight tiny-grid cases."""
+    assert plan_cases.check_table() == {"ws_kernel": 24, "transport_kernel": 21, "deposit": 5, "axis-bound": 6,
+                                        "tiny": 8}
+
+
+@pytest.mark.parametrize("case", plan_cases.CASES, ids=[c.id for c in plan_cases.CASES])
+def test_plan_table(case):
+    """Every case of tests/plan_cases.py gets the plan it states, and with it the kernel
+    instantiation and the deposit regime that tests/test_gpu_instantiations.py runs it for: a
+    changed threshold (MAX_FACE_BYTES, the tile limits, the lean axis bound) fails here instead
+    of leaving a kernel without its GPU case."""
+    p = planprobe.plan(case.scene(), case.scene_grid(), env=case.env)
+    assert p["status"] == abi.OK, p["error"]
+    assert plan_cases.plan_fields(p) == case.plan
+    assert plan_cases.kernel_of(p, case.xsrc, case.flags) == case.kernel
+    assert plan_cases.regime_of(p) == case.regime
+    assert p["n_tiles"] == (plan_cases.tiles_of(case.grid) if plan_cases.tiles_of(case.grid) <= 4096 else 0)
+
+
+def test_design_coverage_table_cites_the_cases():
+    """DESIGN.md §3.3b names, for each instantiation and deposit regime, the test id that runs
+    it: every matrix and deposit case of the table is cited there by its id."""
+    with open(os.path.join(ROOT, "DESIGN.md")) as f:
+        doc = f.read()
+    cases = plan_cases.group("matrix") + plan_cases.group("deposit")
+    missing = [c.id for c in cases if f"`test_case[{c.id}]`" not in doc]
+    assert not missing, missing
+    cited = set(re.findall(r"`test_case\[((?:ws|tr|dep)-[A-Za-z0-9-]+)\]`", doc))
+    assert cited <= set(plan_cases.BY_ID), sorted(cited - set(plan_cases.BY_ID))
 
 
 def test_nested_scenes_never_run_lean():
