@@ -1,5 +1,6 @@
 """Build and run tests/sceneplan_probe.cpp: the engine's device-free scene plan
-(rsmcrt_amd/csrc/sceneplan.h) as a dict, on a machine without a GPU.
+(rsmcrt_amd/csrc/sceneplan.h) as a dict, and the plan's culling grid (cull.h) as arrays, on a
+machine without a GPU.
 
 The probe is host code only (hipcc in host-only mode over the probe, sceneplan.cpp and
 cull.cpp; no kernel object, no libsmcrt.so), cached next to the library and rebuilt
@@ -47,21 +48,49 @@ def _value(v):
         return float.fromhex(v)
 
 
+def _blob(sc, g, dets=(), nodes=None, top=None):
+    nodes = sc.node_array() if nodes is None else nodes
+    top = list(sc.top) if top is None else list(top)
+    return (struct.pack("3i", len(nodes), len(top), len(dets)) + bytes(nodes) + struct.pack(f"{len(top)}i", *top) +
+            bytes(g) + (bytes(S.detector_array(dets)) if dets else b""))
+
+
 def plan(sc, g, dets=(), env=None, nodes=None, top=None):
     """The plan of scene `sc` on grid `g`: ints, floats (exact: the probe prints hex floats) and
     lists of them, plus `status` (abi.OK or an error code) and `error` (its message). `nodes` /
     `top` replace the scene's arrays (invalid scenes)."""
-    nodes = sc.node_array() if nodes is None else nodes
-    top = list(sc.top) if top is None else list(top)
-    blob = (struct.pack("3i", len(nodes), len(top), len(dets)) + bytes(nodes) + struct.pack(f"{len(top)}i", *top) +
-            bytes(g) + (bytes(S.detector_array(dets)) if dets else b""))
     with tempfile.NamedTemporaryFile(suffix=".scene") as f:
-        f.write(blob)
+        f.write(_blob(sc, g, dets, nodes, top))
         f.flush()
         raw = _run(["plan", f.name], env)
     out = {"status": int(raw.pop("status")), "error": raw.pop("error")}
     out.update({k: _value(v) for k, v in raw.items()})
     return out
+
+
+def cull(sc, g, env=None):
+    """The culling grid (cull.h CullHost) of the plan of `sc` on `g`, as the kernels read it: a
+    dict with `enabled`, `n` (cells per axis), `lo`, `cell`, `off` (ncells + 1), `list` (entries
+    x 2 words: top | flags, node), `elb` (float32 per entry), `lb` (per cell) and `always`."""
+    import numpy as np
+    with tempfile.NamedTemporaryFile(suffix=".scene") as f, tempfile.NamedTemporaryFile(suffix=".cull") as out:
+        f.write(_blob(sc, g))
+        f.flush()
+        raw = _run(["cull", f.name, out.name], env)
+        assert int(raw["status"]) == 0, raw["error"]
+        data = out.read()
+    enabled, nx, ny, nz, n_always, _ = struct.unpack_from("6i", data, 0)
+    geo = struct.unpack_from("4d", data, 24)
+    n_off, n_list, n_elb, n_lb = struct.unpack_from("4Q", data, 56)
+    pos = 88
+    res = {"enabled": bool(enabled), "n": (nx, ny, nz), "lo": geo[:3], "cell": geo[3]}
+    for key, dtype, count in (("off", "<u4", n_off), ("list", "<u4", n_list), ("elb", "<f4", n_elb), ("lb", "<f8", n_lb),
+                              ("always", "<i4", n_always)):
+        res[key] = np.frombuffer(data, dtype=dtype, count=count, offset=pos)
+        pos += count * np.dtype(dtype).itemsize
+    assert pos == len(data)
+    res["list"] = res["list"].reshape(-1, 2)
+    return res
 
 
 def slot_depth(lean_or_far, cap_bytes, total_mem, env=None):

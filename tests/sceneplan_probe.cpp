@@ -4,6 +4,10 @@
 //
 //   sceneplan_probe plan FILE   FILE: int32 n_nodes, n_top, n_dets | smcrt_sdf_node[n_nodes] |
 //                               int32 top[n_top] | smcrt_grid | smcrt_detector[n_dets]
+//   sceneplan_probe cull FILE OUT   the plan's culling grid (cull.h CullHost) into OUT: int32 enabled,
+//                               n[3], n_always, pad | double lo[3], cell | uint64 sizes of off, list,
+//                               elb, lb | uint32 off[] | uint32 list[] | float elb[] | double lb[] |
+//                               int32 always[]
 //   sceneplan_probe slots LEAN_OR_FAR CAP_BYTES TOTAL_MEM
 // The SMCRT_* knobs come from the environment, through the readers the library uses.
 #include <cstdio>
@@ -24,7 +28,26 @@ static bool read_n(std::FILE* f, std::vector<T>& v, size_t n) {
   return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
 }
 
-static int plan(const char* path) {
+template <class T>
+static bool write_n(std::FILE* f, const T* v, size_t n) {
+  return n == 0 || std::fwrite(v, sizeof(T), n, f) == n;
+}
+
+// the culling grid the kernels read (smcrt.hip upload_cull copies these arrays as they are)
+static int dump_cull(const CullHost& H, const char* path) {
+  std::FILE* f = std::fopen(path, "wb");
+  if (!f) return 2;
+  const int32_t head[6] = {(int32_t)H.enabled, H.n[0], H.n[1], H.n[2], (int32_t)H.always.size(), 0};
+  const double geo[4] = {H.lo[0], H.lo[1], H.lo[2], H.cell};
+  const uint64_t sizes[4] = {H.off.size(), H.list.size(), H.elb.size(), H.lb.size()};
+  const bool ok = write_n(f, head, 6) && write_n(f, geo, 4) && write_n(f, sizes, 4) &&
+                  write_n(f, H.off.data(), H.off.size()) && write_n(f, H.list.data(), H.list.size()) &&
+                  write_n(f, H.elb.data(), H.elb.size()) && write_n(f, H.lb.data(), H.lb.size()) &&
+                  write_n(f, H.always.data(), H.always.size());
+  return std::fclose(f) == 0 && ok ? 0 : 2;
+}
+
+static int plan(const char* path, const char* cull_out = nullptr) {
   std::FILE* f = std::fopen(path, "rb");
   int32_t hdr[3];
   if (!f || std::fread(hdr, sizeof(int32_t), 3, f) != 3 || hdr[0] < 0 || hdr[1] < 0 || hdr[2] < 0) return 2;
@@ -40,6 +63,7 @@ static int plan(const char* path) {
                             read_knobs(), lim, &p);
   std::printf("status=%d\nerror=%s\n", st, g_last_error.c_str());
   if (st) return 0;
+  if (cull_out) return dump_cull(p.cull, cull_out);
   std::printf("det_total=%lld\nh_det_off=", (long long)p.det_total);
   for (int64_t o : p.h_det_off) std::printf("%lld,", (long long)o);
   std::printf("\nn_prog=%d\nprog_size=%zu\nnested=%d\ncoop_lanes=%d\nctab=%d\ncull=%d\n", p.n_prog, p.prog.size(),
@@ -57,11 +81,12 @@ static int plan(const char* path) {
 int main(int argc, char** argv) {
   const std::string mode = argc > 1 ? argv[1] : "";
   if (mode == "plan" && argc == 3) return plan(argv[2]);
+  if (mode == "cull" && argc == 4) return plan(argv[2], argv[3]);
   if (mode == "slots" && argc == 5) {
     std::printf("slots=%d\n", slot_depth(read_pool_knobs(), std::atoi(argv[2]) != 0, std::strtoull(argv[3], nullptr, 10),
                                          std::strtoull(argv[4], nullptr, 10)));
     return 0;
   }
-  std::fprintf(stderr, "usage: sceneplan_probe plan FILE | slots LEAN_OR_FAR CAP_BYTES TOTAL_MEM\n");
+  std::fprintf(stderr, "usage: sceneplan_probe plan FILE | cull FILE OUT | slots LEAN_OR_FAR CAP_BYTES TOTAL_MEM\n");
   return 2;
 }
