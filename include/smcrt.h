@@ -464,6 +464,16 @@ typedef struct smcrt_kernel_times {
 int smcrt_scene_set_timing(smcrt_scene* scene, int32_t enable);
 int smcrt_scene_kernel_times(smcrt_scene* scene, smcrt_kernel_times* out);
 
+/* The deposit segments (update_grids calls, SMCRT_CTR_GRID_UPDATES) of this scene's finished
+ * launches that the lean path's photon waves deposited themselves because the segment provably
+ * ended inside its start voxel (one path-length record into that voxel), a
+ * running total since the scene was created. Launches still running count once they finish:
+ * call smcrt_scene_check (or smcrt_run) first. SMCRT_WS_INVOXEL=0 at scene creation hands
+ * every segment to a walker wave instead, as scenes with Fresnel interfaces or detectors do
+ * unless SMCRT_WS_INVOXEL=1; the total then stays 0. The tallies are the same either way
+ * (jmean up to the order of its fp64 sums). */
+int smcrt_scene_invoxel_segments(smcrt_scene* scene, int64_t* out);
+
 /* Normalisation of writer.f90:25-52 (normalise_fluence): grid *= nx*ny*nz / nphotons,
  * i.e. (8*xmax*ymax*zmax)/(nphotons*dx*dy*dz). Host-side helper on an fp32 grid. */
 int smcrt_normalise_fluence(float* grid, const smcrt_grid* g, uint64_t nphotons);

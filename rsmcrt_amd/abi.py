@@ -237,4 +237,5 @@ EXPORTED_SYMBOLS = [
     "smcrt_multi_scene", "smcrt_multi_run", "smcrt_multi_accumulate", "smcrt_multi_collect",
     "smcrt_multi_device_photons", "smcrt_multi_destroy", "smcrt_job_run_devices",
     "smcrt_spectral_sample", "smcrt_scene_set_spectral", "smcrt_scene_check",
+    "smcrt_scene_invoxel_segments",
 ]

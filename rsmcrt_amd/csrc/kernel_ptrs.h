@@ -43,9 +43,10 @@ inline const void* transport_kernel_ptr(bool lds_faces, int gm, bool xsrc, bool 
     default: return kinst_transport_1_2(x, c);
   }
 }
-// ws_kernel<lds_faces, gm, xf, slots> (xf: the Fresnel/detector program points; slots 2 or 3, ws.h)
-inline const void* ws_kernel_ptr(bool lds_faces, int gm, bool xf, int slots) {
-  const int x = xf ? 1 : 0;
+// ws_kernel<lds_faces, gm, xf, slots, iv> (xf: the Fresnel/detector program points; slots 2 or 3;
+// iv: the in-voxel segments' code, always in the plain instantiation, ws.h)
+inline const void* ws_kernel_ptr(bool lds_faces, int gm, bool xf, int slots, bool iv) {
+  const int x = xf ? (iv ? 2 : 1) : 0;
   switch ((lds_faces ? 3 : 0) + gm) {
     case 0: return kinst_ws_0_0(x, slots);
     case 1: return kinst_ws_0_1(x, slots);

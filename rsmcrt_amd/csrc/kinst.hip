@@ -17,7 +17,8 @@ namespace smcrt {
 #if KI_P == 1
 // the plain ws_kernel (no Fresnel program points, no detectors)
 const void* KI_NAME(kinst_wsp)(int slots) {
-  return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, false, 3> : (const void*)ws_kernel<KI_F != 0, KI_G, false, 2>;
+  return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, false, 3, true>
+                    : (const void*)ws_kernel<KI_F != 0, KI_G, false, 2, true>;
 }
 #define KI_DIAG_NAME KI_NAME(kinst_diagp)
 #else
@@ -39,8 +40,13 @@ int kinst_ws_photon_lanes() { return (int)WS_NPL; }
 size_t kinst_ws_scratch_bytes(size_t lanes) { return ws_scratch_bytes(lanes); }
 #endif
 
-const void* KI_NAME(kinst_ws)(int xf, int slots) {
-  if (xf) return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, true, 3> : (const void*)ws_kernel<KI_F != 0, KI_G, true, 2>;
+const void* KI_NAME(kinst_ws)(int xf, int slots) {  // xf 2: the XF instantiation with the in-voxel segments' code
+  if (xf == 2)
+    return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, true, 3, true>
+                      : (const void*)ws_kernel<KI_F != 0, KI_G, true, 2, true>;
+  if (xf)
+    return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, true, 3, false>
+                      : (const void*)ws_kernel<KI_F != 0, KI_G, true, 2, false>;
   return KI_NAME(kinst_wsp)(slots);
 }
 #define KI_DIAG_NAME KI_NAME(kinst_diag)

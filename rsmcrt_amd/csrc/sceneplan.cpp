@@ -43,6 +43,8 @@ Knobs read_knobs() {
   k.fused_hist = !is(std::getenv("SMCRT_FUSED_HIST"), "0");
   const char* wsl = std::getenv("SMCRT_WS_SLOTS");
   k.ws_two_slots = wsl && wsl[0] == '2';
+  const char* wi = std::getenv("SMCRT_WS_INVOXEL");
+  k.ws_invoxel = wi ? (is(wi, "0") ? 0 : 1) : -1;
   const char* le = std::getenv("SMCRT_LEAN");
   k.lean_mode = le ? (is(le, "0") ? 0 : 1) : -1;
   const char* lm = std::getenv("SMCRT_DEBUG_LEAN_MARGIN");
@@ -313,6 +315,7 @@ int plan_scene(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top,
     // in the event waves): M3 169.2-169.8 vs 144.0-144.3 (profiles/r05_ws/ab_m3_m5_fresnel_events.txt)
     p.lean_candidate = ok && !p.nested && (p.lean_mode == 1 || (p.lean_mode != 0 && n_dets == 0));
     p.lean_debug = knobs.lean_debug;
+    p.ws_invoxel = knobs.ws_invoxel;
   }
   p.fold_prio = knobs.fold_prio;
   p.cull_log = knobs.cull_log;

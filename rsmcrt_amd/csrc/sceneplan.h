@@ -37,6 +37,7 @@ enum QueueWord : int {
   Q_FOLD_TICKS,          // bk_reduce workgroup run time, s_memrealtime ticks
   Q_LEAN_HAZARDS,        // deferred lean segments that ended in tflag or an error stop (lean.h)
   Q_WATCHDOG,            // the first expired wait: site | (block + 1) << 8
+  Q_INVOXEL,             // segments deposited by ws_kernel's photon waves (invoxel.h)
   Q_COUNT
 };
 constexpr int N_QUEUES = Q_CALLER + 1;  // launch streams: each has a queue head, a KCold ring, a lane scratch
@@ -66,6 +67,7 @@ struct Knobs {  // read_knobs(): at scene creation
   bool fold_prio = true;      // SMCRT_FOLD_PRIO=0: the fold stream at normal priority
   bool fused_hist = true;     // SMCRT_FUSED_HIST=0
   bool ws_two_slots = false;  // SMCRT_WS_SLOTS=2
+  int ws_invoxel = -1;        // SMCRT_WS_INVOXEL: -1 automatic (on, but off for Fresnel/detector scenes), 0 off, 1 on
   int lean_mode = -1;         // SMCRT_LEAN: -1 automatic, 0 off, 1 forced
   uint32_t lean_debug = 0;    // SMCRT_DEBUG_LEAN_MARGIN (tests only): 1 = "0", 2 = "all"
   bool verbose = false;       // SMCRT_VERBOSE
@@ -134,6 +136,7 @@ struct ScenePlan {
   // profiles/r05_ws/ab_m0.txt.)
   int lean_mode = -1;
   uint32_t lean_debug = 0;
+  int ws_invoxel = -1;     // SMCRT_WS_INVOXEL (-1 automatic, 0 off, 1 on; see ws_invoxel_on)
   // the lean path (ws_kernel) serves this scene: a few tops, bucketed deposition, axes below
   // 2^20 cells, its LDS fits (SMCRT_LEAN=0 keeps transport_kernel); the lane-scratch
   // allocation may still veto it (smcrt_scene::lean_ok)
@@ -199,6 +202,9 @@ inline bool launch_binned(const ScenePlan& p, bool has_jmean, uint32_t flags) {
 inline bool launch_lean(bool lean_ok, bool xsrc, uint32_t bucket_tiles, uint32_t flags) {
   return !xsrc && lean_ok && bucket_tiles && (flags & SMCRT_FLAG_PATHLENGTH) && !(flags & SMCRT_FLAG_SURVIVAL_BIAS);
 }
+// ws_kernel's in-voxel segments (ws.h): on by default in the plain instantiation; the XF one
+// (xf: Fresnel interfaces or detectors), which measured slower with them, only when asked for
+inline bool ws_invoxel_on(int knob, bool xf) { return knob < 0 ? !xf : knob != 0; }
 // lean_margin per axis (lean.h, ws.h), with the operations the kernel used to do
 inline void lean_margins(uint32_t lean_debug, const smcrt_grid& g, double lo[3], double hi[3]) {
   const double eps = 1e-8, mf = (lean_debug & 3u) ? 0.0 : 2.0 * eps;

@@ -359,7 +359,8 @@ static void size_grids(smcrt_scene* s) {
   const bool xf = s->fresnel || s->n_dets > 0;
   if (s->lean_ok) {
     hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, ws_kernel_ptr(s->lds_faces, s->grid_mode, xf, s->ws_slots), kinst_ws_threads(), lean_lds(*s));
+        &per_cu, ws_kernel_ptr(s->lds_faces, s->grid_mode, xf, s->ws_slots, ws_invoxel_on(s->ws_invoxel, xf)),
+        kinst_ws_threads(), lean_lds(*s));
     if (oe != hipSuccess || per_cu < 1) per_cu = 1;
     s->grid_blocks_ws = cus * per_cu;
     if (xf) {  // the lane scratch, per launch stream
@@ -615,8 +616,9 @@ static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xs
   if (lean) {
     ++s->lean_launches;
     void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&C};
-    HIPCHK(hipLaunchKernel(ws_kernel_ptr(s->lds_faces, s->grid_mode, s->d_lscratch != nullptr, s->ws_slots), dim3(blocks),
-                           dim3(kinst_ws_threads()), args, lean_lds(*s), stream));
+    const bool xf = s->d_lscratch != nullptr;
+    HIPCHK(hipLaunchKernel(ws_kernel_ptr(s->lds_faces, s->grid_mode, xf, s->ws_slots, ws_invoxel_on(s->ws_invoxel, xf)),
+                           dim3(blocks), dim3(kinst_ws_threads()), args, lean_lds(*s), stream));
   } else {
     const smcrt_detector* a_dets = K.dets;
     const int64_t* a_off = K.det_off;
@@ -795,6 +797,7 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.queue = nullptr;  // (set per launch: enqueue_transport)
   Ch.far_steps = s->d_queue + Q_FAR_STEPS;
   Ch.lean_hazards = s->d_queue + Q_LEAN_HAZARDS;
+  Ch.invoxel_segs = s->d_queue + Q_INVOXEL;
   Ch.lane_scratch = nullptr;  // (per launch stream: enqueue_transport)
   Ch.watchdog = watchdog_word(s);
 #ifdef SMCRT_DIAG
@@ -814,6 +817,7 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   K.rec_pool = nullptr; K.n_chunks = 0; K.hist_tiles = 0; K.bucket_tiles = 0; K.n_buckets = 0;
   K.claim_delay = knobs.claim_delay;
   K.lean_debug = s->lean_debug | (knobs.drop_event ? 4u : 0u);
+  K.ws_invoxel = ws_invoxel_on(s->ws_invoxel, s->d_lscratch != nullptr) ? 1u : 0u;
   lean_margins(K.lean_debug, s->grid, K.lean_lo, K.lean_hi);
   return SMCRT_OK;
 }
@@ -1183,6 +1187,16 @@ int smcrt_scene_kernel_times(smcrt_scene* s, smcrt_kernel_times* out) {
   s->hazards_reported = hz;
   s->t_transport = s->t_deposit = 0.0;
   s->t_launches = 0;
+  return SMCRT_OK;
+}
+
+int smcrt_scene_invoxel_segments(smcrt_scene* s, int64_t* out) {
+  if (!s || !out) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> g(s->mu);
+  HIPCHK(hipSetDevice(s->device));
+  unsigned long long n = 0;  // (a running total: segments of launches still running count later)
+  HIPCHK(hipMemcpy(&n, s->d_queue + Q_INVOXEL, sizeof(n), hipMemcpyDeviceToHost));
+  *out = (int64_t)n;
   return SMCRT_OK;
 }
 

@@ -75,6 +75,7 @@ struct KCold {
   uint32_t* tile_nb;          // bucketed path: buckets claimed per tile
   unsigned long long* far_steps;  // march steps taken by the far-field march (far.h), running total
   unsigned long long* lean_hazards;  // deferred lean segments ending in tflag / a fault (lean.h), running total
+  unsigned long long* invoxel_segs;  // segments deposited by ws_kernel's photon waves (invoxel.h), running total
   double* lane_scratch;       // ws_kernel's per-photon-lane Fresnel/detector state (ws.h WX_*), or null
   // the watchdog (round 6): every cross-wave wait of the kernels is bounded by watchdog_ticks of
   // s_memrealtime (SMCRT_WATCHDOG_MS; 0 = unbounded); the first wait past it stores
@@ -142,6 +143,9 @@ struct KParams {
   // hazards. Bit 2 (SMCRT_DEBUG_DROP_EVENT, tests only): photon lane 0 of block 0 marks its first
   // event queued without queueing it (the hang class the watchdog turns into a counted fault)
   uint32_t lean_debug;
+  // SMCRT_WS_INVOXEL (sceneplan.h ws_invoxel_on): ws_kernel's photon waves deposit the segments that end inside
+  // their start voxel themselves (invoxel.h) instead of handing them to a walker
+  uint32_t ws_invoxel;
   // the lean path's deferral box (lean.h lean_margin, corner coordinates), formed on the host so
   // that the photon waves read six wave-uniform doubles with scalar loads instead of keeping
   // them in VGPRs (they were spilled to scratch and reloaded at every hand-out)

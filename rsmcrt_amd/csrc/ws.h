@@ -57,10 +57,30 @@
 // bucket claims of deposit.h among the walker waves, whose bound is unchanged: only walkers
 // deposit). An emission's position comes back in the start fields of the photon's next slot,
 // which must be free when the emission is queued.
+//
+// In-voxel segments (SMCRT_WS_INVOXEL; by default on in the plain instantiation and off in the XF
+// one, see the template parameter IV). Sphere tracing shortens its steps
+// geometrically towards a surface, so most segments are far shorter than a voxel: on M1
+// (128^3) 65.7 % of the segments make exactly one record, 18.9 % of all records, in runs of
+// 10.5 consecutive segments in one voxel on average. For a segment that invoxel.h proves to end
+// inside its start voxel the whole of update_grids is known to the photon: one record of
+// real(d, sp) * 1 in the start voxel, the cells stay the start cells, no tflag, no error stop.
+// The photon wave applies that itself at the hand-out, before it looks at its slot: no slot,
+// no ring ticket, no walker, no wait, and the segment is never synchronous. The record goes
+// into a per-lane fp64 sum for one voxel (`iv_acc`, `iv_vox`), added to jmean with one fp64
+// atomic when the lane's next in-voxel segment lies in another voxel, when its photon
+// completes and when the wave leaves its loop (by any exit), as far.h's march does; jmean then
+// differs from the fold's sums at rounding level only, as the fold's own order already makes
+// it. The photon's cells: LF_CELLS set means xcell/ycell/zcell are those of its last segment;
+// an in-voxel segment sets them and LF_CELLS, so the cell word that an earlier, still walking
+// deferred segment writes later is not read (ST_ABSORB and the record read a slot's word only
+// without LF_CELLS, and the next handed-out segment clears it as before). The path adds no
+// cross-wave wait, so the watchdog sites and the termination argument above are unchanged.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "invoxel.h"
 #include "lean.h"
 
 namespace smcrt {
@@ -86,6 +106,12 @@ namespace smcrt {
 #ifndef SMCRT_WS_START_CELLS
 #define SMCRT_WS_START_CELLS 1
 #endif
+// a photon lane's pending in-voxel deposits (see "In-voxel segments"): in VGPRs (0), or in LDS (1),
+// 6 KiB per block, which moves grids of about 1024 tiles from three segment slots to two
+#ifndef SMCRT_WS_INVOXEL_LDS
+#define SMCRT_WS_INVOXEL_LDS 0
+#endif
+constexpr uint32_t WS_NO_VOX = 0xFFFFFFFFu;  // no pending in-voxel deposit (a grid has fewer voxels)
 constexpr int WS_WAVES = SMCRT_WS_WAVES;  // waves per block (8: two blocks per CU, 16: one)
 constexpr int WS_THREADS = 64 * WS_WAVES;
 constexpr int WS_PW = SMCRT_WS_PHOTON_WAVES;  // photon waves per block (waves 0 .. WS_PW-1)
@@ -118,6 +144,12 @@ struct WsSharedT {
   uint32_t busy[WS_NPL];                         // bit s: slot s holds a segment in flight
   uint32_t lu[3][WS_NPL];                        // interactions, nscatt, status (LL_*)
   uint32_t wctr[WS_WAVES][LC_N];                 // per-wave counters
+#if SMCRT_WS_INVOXEL_LDS
+  // a photon lane's in-voxel deposits not yet added to jmean: their fp64 sum and their voxel
+  // (WS_NO_VOX: none); only the lane itself touches them
+  double iv_acc[WS_NPL];
+  uint32_t iv_vox[WS_NPL];
+#endif
   // the event queue (see "Event waves" above): per photon lane an in/out slot, and a queue of
   // owner lanes with the ring's sequence lock
   double ev_dir[3][WS_NPL];   // in: direction; out: the scattered (or emitted) direction
@@ -194,7 +226,12 @@ static_assert(WD_N <= 64, "g_diag[64..] belongs to transport_kernel");
 
 // XF: scenes with Fresnel interfaces or detectors (their program points cost the photon waves
 // registers, so the other scenes run an instantiation without them)
-template <bool LDS_FACES, int GM, bool XF, uint32_t SL>
+// IV: the in-voxel segments' code is compiled in (KParams::ws_invoxel then turns it on). The
+// plain instantiation always has it. The XF one exists with and without: its photon waves are
+// the binding role and short of registers, so the code costs it 5 % switched off (scratch 116
+// -> 140 B) and 11 % switched on (M3 158.6-163.0 and 172.3-172.8 vs 181.0-181.8 M photons/s,
+// profiles/r07_invoxel/ab_invoxel.txt); XF scenes run IV only with SMCRT_WS_INVOXEL=1.
+template <bool LDS_FACES, int GM, bool XF, uint32_t SL, bool IV>
 __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void ws_kernel(
     KParams K, const smcrt_sdf_node* __restrict__ nodes, const ProgOp* __restrict__ prog,
     const KCold* __restrict__ C) {
@@ -231,6 +268,10 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
   for (uint32_t i = threadIdx.x; i < WS_NPL; i += WS_THREADS) {
     sh->busy[i] = 0;
     sh->lu[0][i] = sh->lu[1][i] = sh->lu[2][i] = 0;
+#if SMCRT_WS_INVOXEL_LDS
+    sh->iv_acc[i] = 0.0;
+    sh->iv_vox[i] = WS_NO_VOX;
+#endif
   }
   for (uint32_t i = threadIdx.x; i < WS_RING; i += WS_THREADS) sh->meta[i] = 0;
   for (uint32_t i = threadIdx.x; i < WS_EQ; i += WS_THREADS) sh->evq[i] = 0;
@@ -245,7 +286,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
   uint32_t w_iters = 0, w_sdf = 0, w_dep = 0, hazards = 0;
   // per-lane tallies of the frequent counters, summed over the wave at the end (the rare ones
   // go through ws_count into the wave's LDS counters)
-  uint32_t r_upd = 0, r_scat = 0, r_tau = 0, r_abs = 0;
+  uint32_t r_upd = 0, r_scat = 0, r_tau = 0, r_abs = 0, r_inv = 0;
 #ifdef SMCRT_DIAG
   uint64_t wd[WD_N - WD_WITERS] = {};
   uint64_t tprev = __builtin_amdgcn_s_memtime();
@@ -265,6 +306,25 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
     const bool defer_all = (K.lean_debug & 3u) == 2u;
     // SMCRT_DEBUG_DROP_EVENT (tests only): this lane's first event is marked queued, never queued
     bool drop_event = (K.lean_debug & 4u) && blockIdx.x == 0 && pl == 0;
+    // in-voxel segments (see the header): the lane's pending deposits, one voxel at a time
+    const bool invoxel_on = IV && K.ws_invoxel != 0 && (K.flags & SMCRT_FLAG_PATHLENGTH) != 0;
+#if SMCRT_WS_INVOXEL_LDS
+#define WS_IV_ACC (sh->iv_acc[pl])
+#define WS_IV_VOX (sh->iv_vox[pl])
+#else
+    double iv_acc = 0.0;
+    uint32_t iv_vox = WS_NO_VOX;
+#define WS_IV_ACC iv_acc
+#define WS_IV_VOX iv_vox
+#endif
+    auto iv_flush = [&]() {
+      const uint32_t av = WS_IV_VOX;
+      if (av != WS_NO_VOX) {
+        atomic_add_nr(C->jmean + av, WS_IV_ACC);
+        WS_IV_ACC = 0.0;
+        WS_IV_VOX = WS_NO_VOX;
+      }
+    };
     uint64_t wait_t0 = 0;  // (the watchdog: since when every live lane of this wave has waited)
     // the lane scratch (see WX_*): field f of this lane at X[f * xs]
     const size_t xs = (size_t)gridDim.x * WS_NPL;
@@ -498,12 +558,48 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
         bool push = false, sync = false;
         V3 old = v3(0.0, 0.0, 0.0);
         const uint32_t slot = P.seq;
-        if (P.has(LF_REQ) && !(ws_busy(sh, pl) & (1u << slot))) {  // (else: retry next trip)
+        bool inv = false;
+        int32_t ci = -1, cj = -1, ck = -1;
+        if constexpr (IV) {
+          if (P.has(LF_REQ)) {
+            old = v3(P.pos.x + K.xmax, P.pos.y + K.ymax, P.pos.z + K.zmax);
+            ci = cell_of<GM>(old.x, K.nx, K.xmax, K.inv2x, K.fex);
+            cj = cell_of<GM>(old.y, K.ny, K.ymax, K.inv2y, K.fey);
+            ck = cell_of<GM>(old.z, K.nz, K.zmax, K.inv2z, K.fez);
+            // a segment that ends inside its start voxel (invoxel.h; the faces are wall_dist's,
+            // dda_step_r) needs no walker: tested before the slot, so it never waits for one
+            if (invoxel_on && ci != -1 && cj != -1 && ck != -1)
+              inv = invoxel_segment(old.x, old.y, old.z, P.dir.x, P.dir.y, P.dir.z, P.d,
+                                    face<GM>(xf, P.dir.x > 0.0 ? ci : ci - 1, K.fex),
+                                    face<GM>(yf, P.dir.y > 0.0 ? cj : cj - 1, K.fey),
+                                    face<GM>(zf, P.dir.z > 0.0 ? ck : ck - 1, K.fez));
+          }
+        }
+        if (inv) {
+          // update_grids in full: one record, real(d, sp) * 1 into the start voxel; the cells stay
+          // the start cells (newer than those of any segment still in flight: LF_CELLS keeps the
+          // slots' cell words from replacing them), no tflag, no fault
           ++r_upd;
-          old = v3(P.pos.x + K.xmax, P.pos.y + K.ymax, P.pos.z + K.zmax);
-          const int32_t ci = cell_of<GM>(old.x, K.nx, K.xmax, K.inv2x, K.fex),
-                        cj = cell_of<GM>(old.y, K.ny, K.ymax, K.inv2y, K.fey),
-                        ck = cell_of<GM>(old.z, K.nz, K.zmax, K.inv2z, K.fez);
+          ++r_inv;
+          const uint32_t vox = lin(K, ci, cj, ck);
+          if (WS_IV_VOX != vox) {
+            iv_flush();
+            WS_IV_VOX = vox;
+          }
+          WS_IV_ACC = WS_IV_ACC + (double)(float)P.d;
+          if (P.has(LF_MOVE_FWD)) P.pos = P.pos + smul(P.d, P.dir);
+          else if (P.has(LF_MOVE_BACK)) P.pos = P.pos - smul(P.d, P.dir);
+          P.clr(LF_REQ | LF_MOVE_FWD | LF_MOVE_BACK);
+          P.xcell = ci; P.ycell = cj; P.zcell = ck;
+          P.set(LF_CELLS);
+        } else if (P.has(LF_REQ) && !(ws_busy(sh, pl) & (1u << slot))) {  // (else: retry next trip)
+          ++r_upd;
+          if constexpr (!IV) {  // (the start and its cell, once the slot is free)
+            old = v3(P.pos.x + K.xmax, P.pos.y + K.ymax, P.pos.z + K.zmax);
+            ci = cell_of<GM>(old.x, K.nx, K.xmax, K.inv2x, K.fex);
+            cj = cell_of<GM>(old.y, K.ny, K.ymax, K.inv2y, K.fey);
+            ck = cell_of<GM>(old.z, K.nz, K.zmax, K.inv2z, K.fez);
+          }
           // tauint2's move after update_grids (inttau2.f90:98-122, 163-173)
           if (P.has(LF_MOVE_FWD)) P.pos = P.pos + smul(P.d, P.dir);
           else if (P.has(LF_MOVE_BACK)) P.pos = P.pos - smul(P.d, P.dir);
@@ -785,6 +881,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             else if (WLU(LL_STATUS) == 0) { WLU(LL_STATUS) = 2; ws_count(sh, LC_ESCAPED); }
             ws_count(sh, LC_PHOTONS);
             atomicAdd(&sh->wctr[wv][LC_DRAWS], P.rng.draws);
+            iv_flush();  // (the photon's last in-voxel deposits)
 #ifdef SMCRT_DIAG
             if (C->done_time)
               C->done_time[(((uint64_t)P.rng.pid_hi << 32) | P.rng.pid_lo) - C->done_base] = __builtin_amdgcn_s_memrealtime();
@@ -831,6 +928,9 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
       }
       WST(WD_TP_P8);
     }
+    iv_flush();  // (the wave leaves: all photons done, or abort_ / the watchdog)
+#undef WS_IV_ACC
+#undef WS_IV_VOX
 #undef WLU
     if (lane_id == 0) atomicSub(&sh->alive, 1u);  // (after this wave's last push, in its LDS order)
   } else if (wv < WS_PW + WS_EW) {
@@ -1124,17 +1224,18 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
     unsigned long long* const counters = C->counters;
     const uint32_t hz = wave_sum_u32(hazards);
     const uint32_t n_upd = wave_sum_u32(r_upd), n_scat = wave_sum_u32(r_scat), n_tau = wave_sum_u32(r_tau),
-                   n_abs = wave_sum_u32(r_abs);
+                   n_abs = wave_sum_u32(r_abs), n_inv = wave_sum_u32(r_inv);
     if (lane_id == 0) {
       if (hz) {  // reported: smcrt_kernel_times.lean_hazards, and SMCRT_CTR_FAULTS
         atomicAdd(C->dep_ctl + 5, hz);
         atomicAdd(C->lean_hazards, (unsigned long long)hz);
       }
       if (C->dep_ctl && n_upd) atomicAdd(C->dep_ctl + 6, n_upd);  // segments
+      if (n_inv) atomicAdd(C->invoxel_segs, (unsigned long long)n_inv);  // (each also one deposit)
       if (counters) {
         const uint32_t* c = sh->wctr[wv];
         const uint32_t v[SMCRT_NCOUNTERS] = {c[LC_PHOTONS], c[LC_RETRIES], n_scat,        n_abs,          w_sdf,
-                                             w_dep,         n_upd,         n_tau,          c[LC_FRES],     c[LC_REFL],
+                                             w_dep + n_inv, n_upd,         n_tau,          c[LC_FRES],     c[LC_REFL],
                                              c[LC_BABORT],  c[LC_FAULTS] + hz, c[LC_DRAWS], c[LC_HITS],   c[LC_ESCAPED],
                                              w_iters};
         for (int i = 0; i < SMCRT_NCOUNTERS; ++i)

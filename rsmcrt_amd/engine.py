@@ -275,6 +275,17 @@ class Engine:
                 "lean_launches": t.lean_launches, "far_steps": t.far_steps,
                 "fold_cu_ms": t.fold_cu_ms, "lean_hazards": t.lean_hazards}
 
+    def invoxel_segments(self) -> int:
+        """Deposit segments of the scene's finished launches that the lean path's photon waves
+        deposited themselves (they ended inside their start voxel), a running total
+        (smcrt_scene_invoxel_segments); 0 with SMCRT_WS_INVOXEL=0, and for Fresnel or detector
+        scenes unless SMCRT_WS_INVOXEL=1."""
+        fn = load_library().smcrt_scene_invoxel_segments
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        n = C.c_int64()
+        _check(fn(self._h, C.byref(n)))
+        return n.value
+
 
 def pack_layout(grid, n_det_bins: int, fields: int) -> abi.PackLayout:
     lay = abi.PackLayout()
