@@ -205,7 +205,7 @@ typedef struct smcrt_detector {
   int32_t kind;
   int32_t nbins;       /* stored bin count (TOML nbins + 1) */
   int32_t layer;
-  int32_t reserved;
+  int32_t reserved;    /* bit 0: SMCRT_DET_TRACK_HISTORY; the other bits 0 */
   double pos[3];       /* circle/annulus/fibre: centre; camera: p1 (first corner) */
   double dir[3];       /* circle/annulus/fibre: surface normal; camera: n = normalised e2 x e1 */
   double e1[3], e2[3]; /* camera edge vectors */
@@ -219,6 +219,10 @@ typedef struct smcrt_detector {
                           coreDiameter */
 } smcrt_detector;
 
+/* smcrt_detector.reserved, bit 0: the [[detectors]] key trackHistory. In a run with
+ * SMCRT_FLAG_TRACK_PATHS every hit this detector scores files the photon's path so far. */
+#define SMCRT_DET_TRACK_HISTORY 1
+
 /* ----------------------------------------------------------------- run ----------- */
 enum {
   SMCRT_FLAG_PATHLENGTH = 1u << 0,    /* -Dpathlength: path-length jmean deposition (inttau2.f90:408-445) */
@@ -230,12 +234,14 @@ enum {
   SMCRT_FLAG_RECORD_PHOTONS = 1u << 5, /* fill smcrt_tallies.records (debug/parity) */
   SMCRT_FLAG_ASYNC_FOLD = 1u << 6,     /* smcrt_run_device: the jmean fold may finish after later work
                                           on the stream; jmean is complete after smcrt_scene_fence */
-  SMCRT_FLAG_OVERLAP = 1u << 7         /* smcrt_run_device: launches rotate over up to four internal
+  SMCRT_FLAG_OVERLAP = 1u << 7,        /* smcrt_run_device: launches rotate over up to four internal
                                           streams of the scene (two with SMCRT_SLOTS=2 or record pools
                                           above 24 GiB), each after the caller's earlier work, so launch k+1
                                           fills the GPU while launch k's slowest photons finish; every
                                           tally is complete in `stream` order only after
                                           smcrt_scene_fence (implies SMCRT_FLAG_ASYNC_FOLD) */
+  SMCRT_FLAG_TRACK_PATHS = 1u << 8     /* smcrt_run only: record photon paths into the arena configured with
+                                          smcrt_scene_set_path_tracking (see "photon paths" below) */
 };
 
 typedef struct smcrt_run_config {
@@ -383,6 +389,57 @@ int smcrt_scene_set_spectral(smcrt_scene* scene, int32_t top_index, const smcrt_
  * Synchronous: returns when the tallies are in host memory. */
 int smcrt_run(smcrt_scene* scene, const smcrt_source* src, const smcrt_run_config* cfg,
               smcrt_tallies* io);
+
+/* ---- photon paths (the reference's history stack, detector_base.f90:37, historyStack.f90) --
+ * A photon's path is the list of vec4(pos, step) that noBiasPropagation /
+ * survivalBiasPropagation push: the accepted emission position with step 0
+ * (kernelsMod.f90:1954/2032), then every interaction site, before the albedo draw, with step =
+ * scatters so far (:1959/2037): steps 0, 0, 1, 2, ... Surface crossings and the exit point are
+ * not vertices. The path is cleared at emission only (the reference as compiled also zeroes it
+ * in every record_hit, so it never records anything; its documented intent is kept instead).
+ * Two triggers file a path record in a run with SMCRT_FLAG_TRACK_PATHS:
+ *  - a detector with SMCRT_DET_TRACK_HISTORY files the vertices so far at every hit it scores
+ *    (header: the segment that hit); the photon goes on, a later hit files a longer path;
+ *  - photons with global index in [range_first, range_first + range_count) file their whole
+ *    path when they finish (detector = -1, status = the photon's final status).
+ * Records go into an arena of max_paths slots of max_vertices vertices on the device; a path
+ * that finds no slot is counted as dropped, vertices past max_vertices are counted in
+ * n_vertices but not stored (the path is counted as truncated). The ordinary tallies of a
+ * tracking run are those of the same run without the flag. */
+typedef struct smcrt_path_config {
+  uint64_t range_first, range_count; /* the range trigger; range_count 0: none */
+  int32_t max_vertices;              /* 2 .. 1024 vertices stored per path */
+  int32_t reserved;
+  int64_t max_paths;                 /* >= 1 arena slots */
+} smcrt_path_config;
+
+typedef struct smcrt_path {
+  uint64_t photon;     /* global photon index */
+  int32_t detector;    /* index of the detector that was hit, or -1 (range trigger) */
+  uint32_t hit;        /* ordinal of this record among the photon's records (0, 1, ...) */
+  uint32_t n_vertices; /* vertices pushed so far */
+  uint32_t n_stored;   /* min(n_vertices, max_vertices): vertices in the output */
+  uint32_t status;     /* range trigger: smcrt_photon_record.status; detector trigger: 0 */
+  int32_t layer;       /* detector trigger: the hit segment (record_hit's arguments) ... */
+  int64_t offset;      /* the path's first vertex in smcrt_scene_read_paths' `vertices` */
+  double start[3], dir[3], point_sep, weight; /* ... range trigger: final pos, dir, 0, weight */
+} smcrt_path;
+
+/* Configure (or, with cfg NULL, turn off and free) path tracking on a scene: allocates the
+ * arena and the kernels' per-lane vertex scratch. SMCRT_ERR_OOM if they do not fit.
+ * SMCRT_FLAG_TRACK_PATHS is accepted by smcrt_run on a configured scene only; every other
+ * driver (smcrt_run_device, smcrt_run_origins, the escape and inverse drivers, smcrt_multi_*)
+ * and an unconfigured scene answer SMCRT_ERR_INVALID_ARG. Without the flag a configured scene,
+ * and detectors carrying SMCRT_DET_TRACK_HISTORY, run exactly as they do without tracking. */
+int smcrt_scene_set_path_tracking(smcrt_scene* scene, const smcrt_path_config* cfg);
+/* Paths and stored vertices in the arena since the last tracking smcrt_run started (each such
+ * run clears it), paths dropped for want of a slot, stored paths that were truncated. Any
+ * output may be NULL. */
+int smcrt_scene_path_counts(smcrt_scene* scene, int64_t* n_paths, int64_t* n_vertices, int64_t* n_dropped,
+                            int64_t* n_truncated);
+/* The n_paths records sorted by (photon, hit), and their n_vertices stored vertices (4 doubles
+ * each: x, y, z, step) in the same order; paths[i].offset is path i's first vertex. */
+int smcrt_scene_read_paths(smcrt_scene* scene, smcrt_path* paths, double* vertices /* 4 per stored vertex */);
 
 /* Device-resident variant for multi-GPU and benchmarking: launches on `stream`
  * (a hipStream_t; NULL = the legacy default stream) and accumulates into caller-owned
@@ -679,6 +736,17 @@ int smcrt_write_data_f64(const char* filename, const double* array, int32_t nx, 
 int smcrt_write_detector(const char* filename, const smcrt_detector* d, const double* data,
                          const char* id, int64_t nphotons);
 
+/* The paths of smcrt_scene_read_paths as the reference's history stack writes them
+ * (historyStack.f90 obj_writer / ply_writer / json_writer), the type taken from the file name;
+ * any other extension: SMCRT_ERR_UNSUPPORTED ("Unsupported filetype for track History!").
+ * Numbers are es15.8e2. The file is replaced if it exists.
+ *   .obj:  "v x y z" per stored vertex in path order, then one "l i j k ..." polyline (1-based
+ *          indices) per path of two or more vertices;
+ *   .ply:  ASCII, element vertex (float x, y, z; int step) and element edge (0-based vertex1
+ *          vertex2) with their true counts;
+ *   .json: one object, "<photon>_<hit>_<detector>": [[x, y, z], ...]. */
+int smcrt_write_paths(const char* filename, const smcrt_path* paths, int64_t n_paths, const double* vertices);
+
 /* checkpoint (writer.f90:419-455): "tomlfile=<toml_filename>", "photons_run=<n>", then
  * jmean (fp32, nx*ny*nz, Fortran order) raw. */
 int smcrt_write_checkpoint(const char* filename, const char* toml_filename, int64_t photons_run,
@@ -726,6 +794,13 @@ int smcrt_job_info(const smcrt_job* job, smcrt_job_desc* desc);
 int smcrt_job_scene(const smcrt_job* job, smcrt_sdf_node* nodes, int32_t* top, smcrt_detector* dets);
 /* The metadata dict (the values parse_* and finalise set) as TOML text, for NRRD headers. */
 int smcrt_job_metadata(const smcrt_job* job, char* buf, int32_t cap);
+/* The [[detectors]] historyFileName of the first detector with trackHistory = true (default
+ * "photPos.obj"; "" when no detector tracks) copied into buf. A job with such a detector
+ * runs with path tracking on one device: smcrt_job_run writes the paths to
+ * outdir/<stem>_000<ext> (the reference's name for thread 0) and reports dropped and
+ * truncated paths on stderr; SMCRT_PATH_VERTICES (default 64) and SMCRT_PATH_MAX (default
+ * 65536) size the arena. On more than one device it returns SMCRT_ERR_UNSUPPORTED. */
+int smcrt_job_history_filename(const smcrt_job* job, char* buf, int32_t cap);
 /* default_MCRT (kernelsMod.f90:14-82): run_MCRT on `device` (SMCRT_ALL_DEVICES: every
  * visible GPU through smcrt_multi_run), then finalise (:2321-2416).
  * Photons run in batches of checkpoint_every_n; after each, <checkpoint_file> is rewritten

@@ -60,6 +60,10 @@ FLAG_END_EARLY = 1 << 4
 FLAG_RECORD_PHOTONS = 1 << 5
 FLAG_ASYNC_FOLD = 1 << 6
 FLAG_OVERLAP = 1 << 7
+FLAG_TRACK_PATHS = 1 << 8  # smcrt_run only: record photon paths (Engine.set_path_tracking)
+
+# smcrt_detector.reserved, bit 0: the detector files the photon's path at every hit it scores
+DET_TRACK_HISTORY = 1
 
 # counters
 COUNTER_NAMES = [
@@ -167,6 +171,25 @@ class DeviceTallies(C.Structure):
     ]
 
 
+class PathConfig(C.Structure):
+    _fields_ = [("range_first", C.c_uint64), ("range_count", C.c_uint64), ("max_vertices", C.c_int32),
+                ("reserved", C.c_int32), ("max_paths", C.c_int64)]
+
+
+class Path(C.Structure):
+    _fields_ = [("photon", C.c_uint64), ("detector", C.c_int32), ("hit", C.c_uint32), ("n_vertices", C.c_uint32),
+                ("n_stored", C.c_uint32), ("status", C.c_uint32), ("layer", C.c_int32), ("offset", C.c_int64),
+                ("start", C.c_double * 3), ("dir", C.c_double * 3), ("point_sep", C.c_double), ("weight", C.c_double)]
+
+
+# smcrt_path as a numpy dtype (same layout)
+def path_dtype():
+    import numpy as np
+    return np.dtype([("photon", "<u8"), ("detector", "<i4"), ("hit", "<u4"), ("n_vertices", "<u4"),
+                     ("n_stored", "<u4"), ("status", "<u4"), ("layer", "<i4"), ("offset", "<i8"),
+                     ("start", "<f8", 3), ("dir", "<f8", 3), ("point_sep", "<f8"), ("weight", "<f8")])
+
+
 # photon record as a numpy dtype (same layout)
 def record_dtype():
     import numpy as np
@@ -238,4 +261,6 @@ EXPORTED_SYMBOLS = [
     "smcrt_multi_device_photons", "smcrt_multi_destroy", "smcrt_job_run_devices",
     "smcrt_spectral_sample", "smcrt_scene_set_spectral", "smcrt_scene_check",
     "smcrt_scene_invoxel_segments",
+    "smcrt_scene_set_path_tracking", "smcrt_scene_path_counts", "smcrt_scene_read_paths", "smcrt_write_paths",
+    "smcrt_job_history_filename",
 ]

@@ -484,6 +484,8 @@ int smcrt_escape_run(smcrt_scene* scene, const smcrt_source* src, const smcrt_es
   int st = make_sym(cfg, &S);
   if (st) return st;
   if (!scene || !run || !io) return set_error(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  if (run->flags & SMCRT_FLAG_TRACK_PATHS)
+    return set_error(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
   smcrt_grid g;
   int32_t nd = 0;
   if ((st = smcrt_scene_info(scene, &g, nullptr, &nd))) return st;

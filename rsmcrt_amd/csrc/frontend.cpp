@@ -24,6 +24,7 @@
 
 #include "../../include/smcrt.h"
 #include "hosterr.h"
+#include "scene_internal.h"
 #include "mat4.h"
 #include "png.h"
 #include "toml.h"
@@ -159,6 +160,9 @@ struct smcrt_job {
   std::vector<smcrt_detector> dets;
   std::vector<std::string> det_ids;
   std::vector<double> det_targets;  // inverseTarget per detector
+  // historyFileName of the first detector with trackHistory (the reference keeps one stack per
+  // thread, named by the detector that set it up last); "" when no detector tracks
+  std::string history_file;
   // the -DescapeFunction / -DinverseMCRT builds' extra tables (parse.f90:64-70)
   int32_t mode = SMCRT_JOB_DEFAULT;
   smcrt_escape_config esc{};
@@ -739,9 +743,13 @@ void parse_detectors(smcrt_job& J, const Table* root) {  // parse_detectors.f90:
     if (!idv) throw Fail(SMCRT_ERR_INVALID_ARG, "Need to specify a detector ID");
     const std::string id = idv->kind == Value::STRING ? idv->s : std::to_string(idv->i);
     const double target = T::get_real(c, "inverseTarget", -1.0);
-    if (T::get_bool(c, "trackHistory", false)) throw Fail(SMCRT_ERR_UNSUPPORTED, "Track history currently incompatable with OpenMP!");
+    // parse_detectors.f90: trackHistory / historyFileName (default photPos.obj). The reference
+    // stops here under OpenMP; this engine records the paths (smcrt.h "photon paths").
+    const bool track = T::get_bool(c, "trackHistory", false);
+    if (track && J.history_file.empty()) J.history_file = T::get_string(c, "historyFileName", "photPos.obj");
     smcrt_detector d;
     std::memset(&d, 0, sizeof(d));
+    d.reserved = track ? SMCRT_DET_TRACK_HISTORY : 0;
     d.layer = (int32_t)T::get_int(c, "layer", 1);
     double pos[3] = {0, 0, 0}, dir[3] = {0.0, 0.0, -1.0};
     if (type == "circle" || type == "annulus" || type == "fibre") {
@@ -1002,6 +1010,13 @@ int smcrt_job_scene(const smcrt_job* J, smcrt_sdf_node* nodes, int32_t* top, smc
   return SMCRT_OK;
 }
 
+int smcrt_job_history_filename(const smcrt_job* J, char* buf, int32_t cap) {
+  if (!J || !buf || cap < 1) return ffail(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  if ((size_t)cap <= J->history_file.size()) return ffail(SMCRT_ERR_INVALID_ARG, "buffer too small");
+  std::memcpy(buf, J->history_file.c_str(), J->history_file.size() + 1);
+  return SMCRT_OK;
+}
+
 int smcrt_job_metadata(const smcrt_job* J, char* buf, int32_t cap) {
   if (!J || !buf || cap < 1) return ffail(SMCRT_ERR_INVALID_ARG, "bad arguments");
   smcrt_job tmp = *J;
@@ -1110,13 +1125,33 @@ static int job_run_impl(smcrt_job* J0, int32_t device, const std::vector<int32_t
   smcrt_scene* scene = nullptr;
   smcrt_multi* multi = nullptr;
   const smcrt_detector* dp = J->dets.empty() ? nullptr : J->dets.data();
-  int st = devices.empty()
+  // a detector with trackHistory: the job records photon paths, on one device
+  const bool track = !J->history_file.empty();
+  if (track && devices.size() > 1)
+    return ffail(SMCRT_ERR_UNSUPPORTED, "path tracking (trackHistory) runs on one device: multi-GPU collection of paths is not built");
+  smcrt_path_config pcfg;
+  std::memset(&pcfg, 0, sizeof(pcfg));
+  if (track) {
+    smcrt::job_path_knobs(&pcfg.max_vertices, &pcfg.max_paths);
+    if (pcfg.max_vertices < 2 || pcfg.max_vertices > 1024 || pcfg.max_paths < 1)
+      return ffail(SMCRT_ERR_INVALID_ARG, "SMCRT_PATH_VERTICES must lie in 2 .. 1024 and SMCRT_PATH_MAX be >= 1");
+  }
+  const bool single = devices.empty() || (track && devices.size() == 1);
+  if (single && !devices.empty()) device = devices[0];
+  int st = single
                ? smcrt_scene_create(J->nodes.data(), (int32_t)J->nodes.size(), J->top.data(), (int32_t)J->top.size(),
                                     &J->grid, dp, (int32_t)J->dets.size(), device, &scene)
                : smcrt_multi_create(J->nodes.data(), (int32_t)J->nodes.size(), J->top.data(), (int32_t)J->top.size(),
                                     &J->grid, dp, (int32_t)J->dets.size(), devices.data(), (int32_t)devices.size(),
                                     &multi);
+  if (!st && track) {
+    st = smcrt_scene_set_path_tracking(scene, &pcfg);
+    if (st) smcrt_scene_destroy(scene);
+  }
   if (st) return st;
+  std::vector<smcrt_path> paths;     // the paths of every smcrt_run of the job, in run order
+  std::vector<double> path_vertices;
+  int64_t paths_dropped = 0, paths_truncated = 0;
   const size_t nv = (size_t)J->grid.nx * J->grid.ny * J->grid.nz;
   std::vector<double> jm(nv, 0.0), ab(nv, 0.0), em(nv, 0.0);
   int64_t nb = 0;
@@ -1130,7 +1165,8 @@ static int job_run_impl(smcrt_job* J0, int32_t device, const std::vector<int32_t
   smcrt_run_config cfg;
   std::memset(&cfg, 0, sizeof(cfg));
   cfg.seed = (uint64_t)J->iseed;
-  cfg.flags = SMCRT_FLAG_PATHLENGTH | (J->render_source ? SMCRT_FLAG_RENDER_SOURCE : 0);
+  cfg.flags = SMCRT_FLAG_PATHLENGTH | (J->render_source ? SMCRT_FLAG_RENDER_SOURCE : 0) |
+              (track ? SMCRT_FLAG_TRACK_PATHS : 0);
   // checkpoints (run_MCRT, kernelsMod.f90:1862): the reference's thread 0 writes one whenever
   // its j is a multiple of checkpoint_every_n, each replacing the last. Here the GPUs run
   // batches of a multiple of checkpoint_every_n photons, at least MIN_BATCH per GPU (the
@@ -1160,6 +1196,19 @@ static int job_run_impl(smcrt_job* J0, int32_t device, const std::vector<int32_t
     const bool ckpt = J->ckptfreq > 0 && done <= last && done % every == 0;
     if (scene) {
       st = smcrt_run(scene, &J->src, &cfg, &io);
+      if (!st && track) {  // (each tracking run clears the arena: gather its paths now)
+        int64_t np = 0, nvx = 0, nd = 0, nt = 0;
+        st = smcrt_scene_path_counts(scene, &np, &nvx, &nd, &nt);
+        if (!st && np > 0) {
+          const size_t p0 = paths.size(), v0 = path_vertices.size() / 4;
+          paths.resize(p0 + (size_t)np);
+          path_vertices.resize(4 * (v0 + (size_t)nvx));
+          st = smcrt_scene_read_paths(scene, paths.data() + p0, path_vertices.data() + 4 * v0);
+          for (size_t i = p0; i < paths.size(); ++i) paths[i].offset += (int64_t)v0;
+        }
+        paths_dropped += nd;
+        paths_truncated += nt;
+      }
     } else {
       st = smcrt_multi_accumulate(multi, &J->src, &cfg);
       if (!st && (ckpt || done >= J->nphotons)) st = smcrt_multi_collect(multi, &io);
@@ -1178,6 +1227,18 @@ static int job_run_impl(smcrt_job* J0, int32_t device, const std::vector<int32_t
   smcrt_multi_destroy(multi);
   if (st) return st;
   if (nscatt_out) *nscatt_out = nscatt;
+  if (track) {  // <stem>_000<ext>: init_historyStack's name for thread 0 (historyStack.f90:46-47)
+    const std::string& h = J->history_file;
+    const size_t dot = h.find('.');
+    const std::string hname = dot == std::string::npos ? h + "_000" : h.substr(0, dot) + "_000" + h.substr(dot);
+    if (!mkdirs(outdir)) return ffail(SMCRT_ERR_INVALID_ARG, std::string("cannot create ") + outdir);
+    if ((st = smcrt_write_paths((std::string(outdir) + "/" + hname).c_str(), paths.data(), (int64_t)paths.size(),
+                                path_vertices.data())))
+      return st;
+    if (paths_dropped || paths_truncated)
+      std::fprintf(stderr, "[smcrt] path tracking: %lld paths dropped (SMCRT_PATH_MAX), %lld truncated (SMCRT_PATH_VERTICES)\n",
+                   (long long)paths_dropped, (long long)paths_truncated);
+  }
   std::vector<float> jmean(nv), absorb(nv), emission(nv);
   for (size_t i = 0; i < nv; ++i) {
     jmean[i] = (float)jm[i]; absorb[i] = (float)ab[i]; emission[i] = (float)em[i];

@@ -1,7 +1,8 @@
 // kernel_ptrs.h — the transport kernel instantiations, reached through pointers.
 //
 // build.py compiles kinst.hip once per (LDS faces F, grid mode G, part P) with -DKI_F=F -DKI_G=G
-// -DKI_P=P (part 1: the plain ws_kernel, with its own scheduler flags), so
+// -DKI_P=P (part 1: the plain ws_kernel, with its own scheduler flags; part 2, F = 0 only:
+// transport_kernel's HIST instantiations, the photon path recorder of paths.h), so
 // the instantiations of transport_kernel and ws_kernel (kernels.h, ws.h) build in parallel
 // instead of in one translation unit. Each object exports these getters; hipLaunchKernel and
 // the occupancy queries take the host stubs they return.
@@ -28,12 +29,21 @@ SMCRT_KINST_DECL(1, 0)
 SMCRT_KINST_DECL(1, 1)
 SMCRT_KINST_DECL(1, 2)
 #undef SMCRT_KINST_DECL
+#define SMCRT_KINST_HIST_DECL(G)                                  \
+  const void* kinst_transport_hist_0_##G(int xsrc, int coop);     \
+  void kinst_diagh_0_##G(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6);
+SMCRT_KINST_HIST_DECL(0)
+SMCRT_KINST_HIST_DECL(1)
+SMCRT_KINST_HIST_DECL(2)
+#undef SMCRT_KINST_HIST_DECL
 
-// transport_kernel<lds_faces, gm, xsrc, coop>; the general emitter with the COOP machinery
-// (xsrc && coop) exists with faces in device memory only
-inline const void* transport_kernel_ptr(bool lds_faces, int gm, bool xsrc, bool coop) {
-  if (xsrc && coop) lds_faces = false;
+// transport_kernel<lds_faces, gm, xsrc, coop, hist>; the general emitter with the COOP machinery
+// (xsrc && coop) and the path recorder (hist, paths.h) exist with faces in device memory only
+inline const void* transport_kernel_ptr(bool lds_faces, int gm, bool xsrc, bool coop, bool hist = false) {
+  if ((xsrc && coop) || hist) lds_faces = false;
   const int x = xsrc ? 1 : 0, c = coop ? 1 : 0;
+  if (hist) return gm == 0 ? kinst_transport_hist_0_0(x, c) : gm == 1 ? kinst_transport_hist_0_1(x, c)
+                                                                      : kinst_transport_hist_0_2(x, c);
   switch ((lds_faces ? 3 : 0) + gm) {
     case 0: return kinst_transport_0_0(x, c);
     case 1: return kinst_transport_0_1(x, c);
@@ -65,6 +75,7 @@ inline void kinst_diag_gather(unsigned long long* d72, unsigned long long* t9, u
   kinst_diag_1_0(d72, t9, c6); kinst_diag_1_1(d72, t9, c6); kinst_diag_1_2(d72, t9, c6);
   kinst_diagp_0_0(d72, t9, c6); kinst_diagp_0_1(d72, t9, c6); kinst_diagp_0_2(d72, t9, c6);
   kinst_diagp_1_0(d72, t9, c6); kinst_diagp_1_1(d72, t9, c6); kinst_diagp_1_2(d72, t9, c6);
+  kinst_diagh_0_0(d72, t9, c6); kinst_diagh_0_1(d72, t9, c6); kinst_diagh_0_2(d72, t9, c6);
 }
 
 }  // namespace smcrt

@@ -10,6 +10,7 @@
 #include "scene_internal.h"
 #include "transport.h"
 #include "deposit.h"
+#include "paths.h"
 
 using namespace smcrt;
 // ------------------------------------------------------------------ kernel ---------
@@ -80,7 +81,9 @@ constexpr int SOLO_LANES = SMCRT_SOLO_LANES;
 #ifndef SMCRT_WAVES_PER_EU_XSRC
 #define SMCRT_WAVES_PER_EU_XSRC SMCRT_WAVES_PER_EU
 #endif
-template <bool LDS_FACES, int GM, bool XSRC, bool COOP>
+// HIST: the photon path recorder (paths.h, SMCRT_FLAG_TRACK_PATHS). Every line of it is under
+// `if constexpr (HIST)`, so the other instantiations are what they were without it.
+template <bool LDS_FACES, int GM, bool XSRC, bool COOP, bool HIST = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCRT_WAVES_PER_EU_COOP : (XSRC ? SMCRT_WAVES_PER_EU_XSRC : SMCRT_WAVES_PER_EU)))) void transport_kernel(KParams K, const smcrt_sdf_node* __restrict__ nodes,
                                                         const ProgOp* __restrict__ prog,
                                                         const smcrt_detector* __restrict__ dets,
@@ -156,6 +159,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
   uint32_t w_dep = 0, w_sdf = 0, w_iters = 0;  // wave totals (scalar registers)
   uint64_t chunk_base = 0;  // wave-uniform photon chunk
   uint32_t chunk_left = 0;
+  // HIST: this photon's path (vertex and record counts). An empty type otherwise: even a dead
+  // PathLane changed the register allocation of the other instantiations.
+  [[maybe_unused]] std::conditional_t<HIST, PathLane, NoPathLane> H;
 
 #ifdef SMCRT_DIAG
   unsigned long long t_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -663,7 +669,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
       if constexpr (XSRC) {
         if (C->plan.det_totals) tot = C->plan.det_totals + (uint64_t)LU(LU_ORIGIN) * (uint64_t)K.n_dets;
       }
-      LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, rec_start, L.dir, rec_sep, L.layer, L.weight, tot);
+      if constexpr (HIST) {  // a tracking detector files the path so far at each hit it scores
+        auto file = [&](int32_t di, const smcrt_detector* D) {
+          if (D->reserved & SMCRT_DET_TRACK_HISTORY)
+            hist_flush(C, H, ((uint64_t)L.rng.pid_hi << 32) | L.rng.pid_lo, di, 0u, rec_start, L.dir, rec_sep, L.layer,
+                       L.weight);
+        };
+        LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, rec_start, L.dir, rec_sep, L.layer, L.weight, tot, file);
+      } else {
+        LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, rec_start, L.dir, rec_sep, L.layer, L.weight, tot);
+      }
     }
 
     // ---- P6: tauint2 write-back checks, :341-362 -----------------------------------------
@@ -693,6 +708,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
           } else if (++LU(LU_INTER) > (uint32_t)MAX_INTERACTIONS) {
             L.fault = true; L.st = ST_DONE;
           } else {
+            // the interaction site, before the draw: step = scatters so far (kernelsMod.f90:1959/2037)
+            if constexpr (HIST) hist_push(C, H, L.pos, (double)LU(LU_NSCATT));
             const double ran = L.rng.next(K.key0, K.key1);
             const TopProps pr = props[L.layer - 1];
             bool sc = false;
@@ -762,6 +779,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
             }
             if (!L.fault && (K.flags & SMCRT_FLAG_RENDER_SOURCE)) add_cell(K, C->emission, L, 1.0);
           }
+          if constexpr (HIST) {  // a new path: the accepted emission position, step 0 (:1954/2032)
+            H.n = 0; H.hit = 0;
+            if (!L.fault) hist_push(C, H, L.pos, 0.0);
+          }
           if (L.fault) L.st = ST_DONE;
           else { L.st = ST_LAYER; L.pend = true; }
         }
@@ -787,6 +808,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
             r->bounces = LU(LU_BOUNCES);
             r->draws = L.rng.draws;
             r->status = LU(LU_STATUS);
+          }
+          if constexpr (HIST) {  // the range trigger: the whole path of a photon of the tracked range
+            const uint64_t pid = ((uint64_t)L.rng.pid_hi << 32) | L.rng.pid_lo;
+            if (pid - C->range_first < C->range_count)
+              hist_flush(C, H, pid, -1, LU(LU_STATUS), L.pos, L.dir, 0.0, L.layer, L.weight);
           }
           L.tflag = false; L.fault = false;
           L.st = ST_FETCH;

@@ -1,12 +1,15 @@
 // kinst.hip — one (LDS faces, grid mode) slice of the transport kernel instantiations.
-// Compiled twelve times by build.py (-DKI_F=0/1 -DKI_G=0/1/2 -DKI_P=0/1); see kernel_ptrs.h.
+// Compiled fifteen times by build.py (-DKI_F=0/1 -DKI_G=0/1/2 -DKI_P=0/1, and -DKI_P=2 with
+// -DKI_F=0); see kernel_ptrs.h.
 // Part 0 holds transport_kernel and the XF ws_kernel, part 1 the plain ws_kernel (the lean path
-// of M1), which build.py compiles with its own scheduler flags (see UNITS there).
+// of M1), which build.py compiles with its own scheduler flags (see UNITS there), part 2 the
+// HIST instantiations of transport_kernel (the photon path recorder, paths.h; faces in device
+// memory only), in units of their own so that they build beside the others.
 #include "kernels.h"
 #include "kernel_ptrs.h"
 
 #if !defined(KI_F) || !defined(KI_G) || !defined(KI_P)
-#error "kinst.hip is compiled with -DKI_F=<0|1> -DKI_G=<0|1|2> -DKI_P=<0|1> (rsmcrt_amd/build.py)"
+#error "kinst.hip is compiled with -DKI_F=<0|1> -DKI_G=<0|1|2> -DKI_P=<0|1|2> (rsmcrt_amd/build.py)"
 #endif
 #define KI_NAME3(a, f, g) a##_##f##_##g
 #define KI_NAME2(a, f, g) KI_NAME3(a, f, g)
@@ -14,7 +17,18 @@
 
 namespace smcrt {
 
-#if KI_P == 1
+#if KI_P == 2
+#if KI_F != 0
+#error "the HIST instantiations (KI_P=2) exist with KI_F=0 only"
+#endif
+const void* KI_NAME(kinst_transport_hist)(int xsrc, int coop) {
+  if (xsrc && coop) return (const void*)transport_kernel<false, KI_G, true, true, true>;
+  if (xsrc) return (const void*)transport_kernel<false, KI_G, true, false, true>;
+  if (coop) return (const void*)transport_kernel<false, KI_G, false, true, true>;
+  return (const void*)transport_kernel<false, KI_G, false, false, true>;
+}
+#define KI_DIAG_NAME KI_NAME(kinst_diagh)
+#elif KI_P == 1
 // the plain ws_kernel (no Fresnel program points, no detectors)
 const void* KI_NAME(kinst_wsp)(int slots) {
   return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, false, 3, true>

@@ -22,4 +22,7 @@ void* scene_stream(const smcrt_scene* s);
 // scene_inflight < scene_depth
 int scene_inflight(smcrt_scene* s);
 int scene_depth(const smcrt_scene* s);
+// smcrt_job_run's path arena: SMCRT_PATH_VERTICES and SMCRT_PATH_MAX, read where the other
+// launch knobs are (sceneplan.cpp read_launch_knobs)
+void job_path_knobs(int32_t* max_vertices, int64_t* max_paths);
 }  // namespace smcrt

@@ -63,7 +63,15 @@ LaunchKnobs read_launch_knobs() {
   if (const char* cd = std::getenv("SMCRT_DEBUG_CLAIM_DELAY")) k.claim_delay = (uint32_t)std::strtoul(cd, nullptr, 10);
   const char* de = std::getenv("SMCRT_DEBUG_DROP_EVENT");
   k.drop_event = de && de[0] == '1';
+  if (const char* pv = std::getenv("SMCRT_PATH_VERTICES")) k.path_vertices = (int32_t)std::strtol(pv, nullptr, 10);
+  if (const char* pm = std::getenv("SMCRT_PATH_MAX")) k.path_max = (int64_t)std::strtoll(pm, nullptr, 10);
   return k;
+}
+
+void job_path_knobs(int32_t* max_vertices, int64_t* max_paths) {
+  const LaunchKnobs k = read_launch_knobs();
+  *max_vertices = k.path_vertices;
+  *max_paths = k.path_max;
 }
 
 PoolKnobs read_pool_knobs() {

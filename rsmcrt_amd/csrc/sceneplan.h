@@ -73,6 +73,8 @@ struct Knobs {  // read_knobs(): at scene creation
   bool verbose = false;       // SMCRT_VERBOSE
 };
 struct LaunchKnobs {  // read_launch_knobs(): at every launch
+  int32_t path_vertices = 64;  // SMCRT_PATH_VERTICES: smcrt_job_run's vertices per path (2 .. 1024)
+  int64_t path_max = 65536;    // SMCRT_PATH_MAX: smcrt_job_run's arena slots (>= 1)
   double watchdog_ms = DEFAULT_WATCHDOG_MS;  // SMCRT_WATCHDOG_MS; 0: unbounded waits
   uint32_t claim_delay = 0;  // SMCRT_DEBUG_CLAIM_DELAY (tests only)
   bool drop_event = false;   // SMCRT_DEBUG_DROP_EVENT=1 (tests only: the watchdog's proof)
@@ -161,10 +163,11 @@ inline size_t lean_lds(const ScenePlan& p) {
 inline uint32_t dep_words(const ScenePlan& p) { return p.bucketed ? 2 * p.n_tiles : 4 * p.hist_tiles; }
 // Dynamic LDS of the transport kernel: staged props + faces, detector start points, then the
 // deposit words, then the coop table.
-inline size_t transport_lds(const ScenePlan& p, uint32_t dep_words, bool xsrc) {
+inline size_t transport_lds(const ScenePlan& p, uint32_t dep_words, bool xsrc, bool hist = false) {
   const bool ctab = !p.ctab.empty() && p.coop_lanes > 0;  // the COOP instantiations stage it
-  // (the general emitter with the COOP machinery keeps its faces in device memory, kernel_ptrs.h)
-  const bool faces = p.lds_faces && !(xsrc && p.coop_lanes > 0);
+  // (the general emitter with the COOP machinery and the path recorder keep their faces in
+  // device memory, kernel_ptrs.h)
+  const bool faces = p.lds_faces && !(xsrc && p.coop_lanes > 0) && !hist;
   return (faces ? p.face_bytes : 0) + (p.n_dets ? 3 * 256 * sizeof(double) : 0) +
          (size_t)dep_words * sizeof(uint32_t) + (ctab ? CTAB_DOUBLES * sizeof(double) : 0);
 }
@@ -198,9 +201,11 @@ inline bool launch_binned(const ScenePlan& p, bool has_jmean, uint32_t flags) {
          !p.force_atomic;
 }
 // the lean path (ws_kernel, ws.h) when the scene and the run qualify: bucketed path-length
-// deposition, unit weights (no survival bias), a plain source
+// deposition, unit weights (no survival bias), a plain source, no path tracking (ws_kernel has
+// no recorder)
 inline bool launch_lean(bool lean_ok, bool xsrc, uint32_t bucket_tiles, uint32_t flags) {
-  return !xsrc && lean_ok && bucket_tiles && (flags & SMCRT_FLAG_PATHLENGTH) && !(flags & SMCRT_FLAG_SURVIVAL_BIAS);
+  return !xsrc && lean_ok && bucket_tiles && (flags & SMCRT_FLAG_PATHLENGTH) &&
+         !(flags & (SMCRT_FLAG_SURVIVAL_BIAS | SMCRT_FLAG_TRACK_PATHS));
 }
 // ws_kernel's in-voxel segments (ws.h): on by default in the plain instantiation; the XF one
 // (xf: Fresnel interfaces or detectors), which measured slower with them, only when asked for

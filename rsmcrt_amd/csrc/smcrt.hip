@@ -168,6 +168,17 @@ struct smcrt_scene : ScenePlan {
   size_t tev_used = 0;
   double t_transport = 0.0, t_deposit = 0.0;
   int64_t t_launches = 0;
+  // photon paths (smcrt_scene_set_path_tracking; paths.h): the lanes' vertex scratch, sized for
+  // the largest grid of a tracking launch (a tracking run's launches are serial on s->stream),
+  // the arena of path_cfg.max_paths slots with its headers, and the counters
+  // [claimed, dropped, truncated]
+  bool path_on = false;
+  smcrt_path_config path_cfg{};
+  DevBuf<double> d_hist_scratch, d_path_vertices;
+  DevBuf<smcrt_path> d_path_headers;
+  DevBuf<unsigned long long> d_path_ctl;
+  uint64_t hist_lanes = 0;
+  int grid_blocks_hist[2] = {0, 0};  // the HIST instantiations' grids (plain, XSRC)
   std::mutex mu;
 };
 
@@ -197,11 +208,11 @@ static hipError_t harvest_times(smcrt_scene* s) {
 // and culling; it costs registers (scratch spills), so small scenes never pay for it. With the
 // general emitter (XSRC: other sources, batched origins, composites below the top level) that
 // is transport_kernel<.., true, true> (round 4; before, such scenes ran the serial EVAL).
-static const void* transport_fn(const smcrt_scene* s, bool xsrc) {
+static const void* transport_fn(const smcrt_scene* s, bool xsrc, bool hist = false) {
   // (the general emitter with the COOP machinery is instantiated with faces in device memory
   // only: three kernels instead of six, the library's build time, for the rare scenes that run
   // it; transport_lds follows)
-  return transport_kernel_ptr(s->lds_faces, s->grid_mode, xsrc, s->coop_lanes > 0);
+  return transport_kernel_ptr(s->lds_faces, s->grid_mode, xsrc, s->coop_lanes > 0, hist);
 }
 
 // ---- the watchdog (transport.h watchdog_expired): d_queue[Q_WATCHDOG] holds the first
@@ -608,8 +619,10 @@ static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xs
   const uint64_t waves_needed = (Ch.n_photons + 63) / 64;
   const uint64_t blocks_needed = (waves_needed + 3) / 4;
   const uint64_t ws_needed = (Ch.n_photons + kinst_ws_photon_lanes() - 1) / kinst_ws_photon_lanes();
+  const bool hist = (K.flags & SMCRT_FLAG_TRACK_PATHS) && s->path_on;  // (never lean: launch_lean)
   const int blocks = (int)std::min<uint64_t>(
-      (uint64_t)(lean ? s->grid_blocks_ws : (xsrc ? s->grid_blocks_x : s->grid_blocks)),
+      (uint64_t)(lean ? s->grid_blocks_ws
+                      : hist ? s->grid_blocks_hist[xsrc ? 1 : 0] : (xsrc ? s->grid_blocks_x : s->grid_blocks)),
       std::max<uint64_t>(1, lean ? ws_needed : blocks_needed));
   const smcrt_sdf_node* a_nodes = K.nodes;
   const ProgOp* a_prog = K.prog;
@@ -623,7 +636,8 @@ static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xs
     const smcrt_detector* a_dets = K.dets;
     const int64_t* a_off = K.det_off;
     void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&a_dets, (void*)&a_off, (void*)&C};
-    HIPCHK(hipLaunchKernel(transport_fn(s, xsrc), dim3(blocks), dim3(256), args, transport_lds(*s, dep_words(*s), xsrc), stream));
+    HIPCHK(hipLaunchKernel(transport_fn(s, xsrc, hist), dim3(blocks), dim3(256), args,
+                           transport_lds(*s, dep_words(*s), xsrc, hist), stream));
   }
   HIPCHK(hipGetLastError());
   if (ev) HIPCHK(hipEventRecord(ev[1], stream));
@@ -800,6 +814,16 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.invoxel_segs = s->d_queue + Q_INVOXEL;
   Ch.lane_scratch = nullptr;  // (per launch stream: enqueue_transport)
   Ch.watchdog = watchdog_word(s);
+  const bool hist = (cfg->flags & SMCRT_FLAG_TRACK_PATHS) && s->path_on;
+  Ch.hist_scratch = hist ? (double*)s->d_hist_scratch : nullptr;
+  Ch.path_vertices = hist ? (double*)s->d_path_vertices : nullptr;
+  Ch.path_headers = hist ? (smcrt_path*)s->d_path_headers : nullptr;
+  Ch.path_ctl = hist ? (unsigned long long*)s->d_path_ctl : nullptr;
+  Ch.hist_lanes = hist ? s->hist_lanes : 0;
+  Ch.path_max = hist ? (uint64_t)s->path_cfg.max_paths : 0;
+  Ch.range_first = hist ? s->path_cfg.range_first : 0;
+  Ch.range_count = hist ? s->path_cfg.range_count : 0;
+  Ch.hist_max_vertices = hist ? (uint32_t)s->path_cfg.max_vertices : 0;
 #ifdef SMCRT_DIAG
   Ch.done_time = nullptr;
   Ch.done_base = cfg->first_photon;
@@ -945,6 +969,8 @@ int smcrt_run_device(smcrt_scene* s, const smcrt_source* src, const smcrt_run_co
                      smcrt_device_tallies* dev, void* stream) {
   g_last_error.clear();
   if (!s || !src || !cfg || !dev) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  if (cfg->flags & SMCRT_FLAG_TRACK_PATHS)
+    return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
   std::lock_guard<std::mutex> g(s->mu);
   HIPCHK(hipSetDevice(s->device));
   return launch(s, src, cfg, *dev, (hipStream_t)stream);
@@ -1030,7 +1056,12 @@ int smcrt_run(smcrt_scene* s, const smcrt_source* src, const smcrt_run_config* c
   g_last_error.clear();
   if (!s || !src || !cfg || !io) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
   std::lock_guard<std::mutex> g(s->mu);
+  const bool track = (cfg->flags & SMCRT_FLAG_TRACK_PATHS) != 0;
+  if (track && !s->path_on)
+    return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS needs smcrt_scene_set_path_tracking first");
   HIPCHK(hipSetDevice(s->device));
+  if (track)  // a tracking run starts with an empty arena
+    HIPCHK(hipMemsetAsync(s->d_path_ctl, 0, 3 * sizeof(unsigned long long), s->stream));
   return run_sync(s, src, cfg, io, nullptr);
 }
 
@@ -1039,6 +1070,8 @@ int smcrt_run_origins(smcrt_scene* s, const smcrt_source* src, const double* ori
   g_last_error.clear();
   if (!s || !cfg || !io || (n_origins > 0 && !origins)) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
   if (n_origins < 0) return fail(SMCRT_ERR_INVALID_ARG, "n_origins < 0");
+  if (cfg->flags & SMCRT_FLAG_TRACK_PATHS)
+    return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
   if (cfg->flags & SMCRT_FLAG_RECORD_PHOTONS) return fail(SMCRT_ERR_INVALID_ARG, "photon records are not kept for batched origins");
   if (n_origins > 0xFFFFFFFFll) return fail(SMCRT_ERR_INVALID_ARG, "more than 2^32 origins");
   if (n_origins == 0 || cfg->n_photons == 0) return SMCRT_OK;
@@ -1197,6 +1230,115 @@ int smcrt_scene_invoxel_segments(smcrt_scene* s, int64_t* out) {
   unsigned long long n = 0;  // (a running total: segments of launches still running count later)
   HIPCHK(hipMemcpy(&n, s->d_queue + Q_INVOXEL, sizeof(n), hipMemcpyDeviceToHost));
   *out = (int64_t)n;
+  return SMCRT_OK;
+}
+
+// ---- photon paths (paths.h) ---------------------------------------------------------
+static void release_paths(smcrt_scene* s) {
+  s->path_on = false;
+  s->d_hist_scratch.reset(); s->d_path_vertices.reset(); s->d_path_headers.reset(); s->d_path_ctl.reset();
+  s->hist_lanes = 0;
+}
+
+int smcrt_scene_set_path_tracking(smcrt_scene* s, const smcrt_path_config* cfg) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  if (cfg) {  // (decided before any device call)
+    if (cfg->max_vertices < 2 || cfg->max_vertices > 1024)
+      return fail(SMCRT_ERR_INVALID_ARG, "path tracking: max_vertices must lie in 2 .. 1024");
+    if (cfg->max_paths < 1) return fail(SMCRT_ERR_INVALID_ARG, "path tracking: max_paths must be >= 1");
+    if (cfg->range_count > UINT64_MAX - cfg->range_first)
+      return fail(SMCRT_ERR_INVALID_ARG, "path tracking: the photon range overflows");
+  }
+  std::lock_guard<std::mutex> g(s->mu);
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));  // (no launch of this scene may still use the buffers)
+  release_paths(s);
+  if (!cfg) return SMCRT_OK;
+  int cus = s->n_cus;
+  for (int x = 0; x < 2; ++x) {  // the HIST instantiations' persistent grids
+    int per_cu = 0;
+    const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, transport_fn(s, x == 1, true), 256,
+                                                                       transport_lds(*s, dep_words(*s), x == 1, true));
+    if (oe != hipSuccess || per_cu < 1) per_cu = 1;
+    s->grid_blocks_hist[x] = cus * per_cu;
+  }
+  const uint64_t lanes = (uint64_t)std::max(s->grid_blocks_hist[0], s->grid_blocks_hist[1]) * 256ull;
+  const uint64_t mv = (uint64_t)cfg->max_vertices, mp = (uint64_t)cfg->max_paths;
+  if (mp > (1ull << 40) / mv) return fail(SMCRT_ERR_OOM, "path tracking: the arena does not fit");
+  int st;
+  if ((st = dalloc(s->d_hist_scratch, (size_t)(lanes * mv * 4))) || (st = dalloc(s->d_path_vertices, (size_t)(mp * mv * 4))) ||
+      (st = dalloc(s->d_path_headers, (size_t)mp)) || (st = dalloc(s->d_path_ctl, 3))) {
+    (void)hipGetLastError();
+    release_paths(s);
+    return st;
+  }
+  HIPCHK(hipMemset(s->d_path_ctl, 0, 3 * sizeof(unsigned long long)));
+  s->path_cfg = *cfg;
+  s->hist_lanes = lanes;
+  s->path_on = true;
+  return SMCRT_OK;
+}
+
+// The arena's counters and headers (the used slots) after the scene's launches. Caller holds s->mu.
+static int fetch_paths(smcrt_scene* s, unsigned long long ctl[3], std::vector<smcrt_path>& hdr) {
+  if (!s->path_on) return fail(SMCRT_ERR_INVALID_ARG, "path tracking is not configured on this scene");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(hipMemcpy(ctl, s->d_path_ctl, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  const uint64_t n = std::min<uint64_t>(ctl[0], (uint64_t)s->path_cfg.max_paths);
+  hdr.resize((size_t)n);
+  if (n) HIPCHK(hipMemcpy(hdr.data(), s->d_path_headers, (size_t)n * sizeof(smcrt_path), hipMemcpyDeviceToHost));
+  for (smcrt_path& p : hdr)  // (the library's own bound, whatever the device wrote)
+    p.n_stored = std::min<uint32_t>(p.n_stored, (uint32_t)s->path_cfg.max_vertices);
+  return SMCRT_OK;
+}
+
+int smcrt_scene_path_counts(smcrt_scene* s, int64_t* n_paths, int64_t* n_vertices, int64_t* n_dropped,
+                            int64_t* n_truncated) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  std::lock_guard<std::mutex> g(s->mu);
+  unsigned long long ctl[3];
+  std::vector<smcrt_path> hdr;
+  if (const int st = fetch_paths(s, ctl, hdr)) return st;
+  int64_t nv = 0;
+  for (const smcrt_path& p : hdr) nv += p.n_stored;
+  if (n_paths) *n_paths = (int64_t)hdr.size();
+  if (n_vertices) *n_vertices = nv;
+  if (n_dropped) *n_dropped = (int64_t)ctl[1];
+  if (n_truncated) *n_truncated = (int64_t)ctl[2];
+  return SMCRT_OK;
+}
+
+int smcrt_scene_read_paths(smcrt_scene* s, smcrt_path* paths, double* vertices) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  std::lock_guard<std::mutex> g(s->mu);
+  unsigned long long ctl[3];
+  std::vector<smcrt_path> hdr;
+  if (const int st = fetch_paths(s, ctl, hdr)) return st;
+  if (hdr.empty()) return SMCRT_OK;
+  if (!paths || !vertices) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  // arena order is whatever the atomics gave: (photon, hit) makes the output deterministic
+  std::vector<size_t> order(hdr.size());
+  for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    if (hdr[a].photon != hdr[b].photon) return hdr[a].photon < hdr[b].photon;
+    if (hdr[a].hit != hdr[b].hit) return hdr[a].hit < hdr[b].hit;
+    return a < b;
+  });
+  const size_t mv = (size_t)s->path_cfg.max_vertices;
+  std::vector<double> arena(hdr.size() * mv * 4);
+  HIPCHK(hipMemcpy(arena.data(), s->d_path_vertices, arena.size() * sizeof(double), hipMemcpyDeviceToHost));
+  int64_t off = 0;
+  for (size_t k = 0; k < order.size(); ++k) {
+    const size_t slot = order[k];
+    paths[k] = hdr[slot];
+    paths[k].offset = off;
+    std::memcpy(vertices + 4 * off, arena.data() + slot * mv * 4, (size_t)hdr[slot].n_stored * 4 * sizeof(double));
+    off += hdr[slot].n_stored;
+  }
   return SMCRT_OK;
 }
 

@@ -90,6 +90,16 @@ struct KCold {
   uint64_t done_base;
 #endif
   SrcPlan plan;               // the general emitter's constants (XSRC instantiations only)
+  // photon paths (SMCRT_FLAG_TRACK_PATHS; read by the HIST instantiations of transport_kernel
+  // only, all null / 0 otherwise). Kept last so that every other field stays where it was.
+  double* hist_scratch;       // [hist_lanes][hist_max_vertices][4]: the path of each lane's photon so far
+  double* path_vertices;      // the arena: [path_max][hist_max_vertices][4]
+  smcrt_path* path_headers;   // [path_max]
+  unsigned long long* path_ctl;  // [0] slots claimed, [1] paths dropped, [2] stored paths truncated
+  uint64_t hist_lanes;        // lanes the scratch holds (the largest grid of a tracking launch)
+  uint64_t path_max;          // arena slots
+  uint64_t range_first, range_count;  // the range trigger
+  uint32_t hist_max_vertices;
 };
 
 // watchdog sites (KCold::watchdog bits 0-7; smcrt.hip names them)
@@ -228,15 +238,21 @@ __device__ __forceinline__ int64_t f_int(double x) {
   return (int64_t)x;
 }
 
+struct NoHitHook {  // record_hits' default: nothing happens at a hit but the tally
+  __device__ __forceinline__ void operator()(int32_t, const smcrt_detector*) const {}
+};
 // record_hit on every detector for one path segment (detector_base.f90:137-235,
 // detectors.f90:147-469). Returns the number of bin increments.
 // `totals` (batched point sources): add each hit to totals[detector] (total_dect,
 // detector_base.f90) instead of to its bin.
+// `on_hit(detector index, detector)` runs where a bin is incremented, in detector order (the
+// HIST instantiations file a photon path there; everything else passes nothing).
+template <class OnHit = NoHitHook>
 __device__ __forceinline__ uint32_t record_hits(const KParams& K, double* det_bins,
                                                 const smcrt_detector* __restrict__ dets,
                                                 const int64_t* __restrict__ det_off, V3 start, V3 dir,
                                                 double pointSep, int32_t layer, double weight,
-                                                double* totals = nullptr) {
+                                                double* totals = nullptr, OnHit on_hit = OnHit()) {
   uint32_t hits = 0;
   double value1D = (double)layer;  // hit_t%value1D <- packet%layer
   for (int32_t di = 0; di < K.n_dets; ++di) {
@@ -333,6 +349,7 @@ __device__ __forceinline__ uint32_t record_hits(const KParams& K, double* det_bi
       if (totals) atomic_add_nr(totals + di, w);
       else if (data) atomic_add_nr(data + bin, w);
       ++hits;
+      on_hit(di, D);
     }
   }
   return hits;

@@ -181,4 +181,77 @@ int smcrt_write_checkpoint(const char* filename, const char* toml_filename, int6
   return SMCRT_OK;
 }
 
+// The history stack's writers (historyStack.f90 obj_writer :184-226, ply_writer :228-273,
+// json_writer :275-310), for all paths at once: the reference appends path by path and patches
+// the ply counts with sed afterwards. The type is taken from the name as init_historyStack
+// does (:51-58: the first of obj, ply, json the name contains).
+int smcrt_write_paths(const char* filename, const smcrt_path* paths, int64_t n_paths, const double* vertices) {
+  if (!filename || n_paths < 0 || (n_paths > 0 && (!paths || !vertices))) return wfail(SMCRT_ERR_INVALID_ARG, "bad arguments");
+  const std::string f = filename;
+  const size_t sl = f.find_last_of('/');
+  const std::string name = sl == std::string::npos ? f : f.substr(sl + 1);
+  const int type = name.find("obj") != std::string::npos ? 0 : name.find("ply") != std::string::npos ? 1
+                   : name.find("json") != std::string::npos ? 2 : -1;
+  if (type < 0) return wfail(SMCRT_ERR_UNSUPPORTED, "Unsupported filetype for track History!");
+  int64_t nv = 0, ne = 0;
+  for (int64_t i = 0; i < n_paths; ++i) {
+    nv += paths[i].n_stored;
+    if (paths[i].n_stored >= 2) ne += paths[i].n_stored - 1;
+  }
+  std::string out;
+  char b[96];
+  auto vert = [&](int64_t i, uint32_t k) { return vertices + 4 * (paths[i].offset + (int64_t)k); };
+  if (type == 0) {  // "(a,1x,3(es15.8e2,1x))", then the polylines
+    for (int64_t i = 0; i < n_paths; ++i)
+      for (uint32_t k = 0; k < paths[i].n_stored; ++k) {
+        const double* v = vert(i, k);
+        std::snprintf(b, sizeof b, "v %15.8E %15.8E %15.8E \n", v[0], v[1], v[2]);
+        out += b;
+      }
+    int64_t first = 1;  // obj indices are 1-based
+    for (int64_t i = 0; i < n_paths; ++i) {
+      if (paths[i].n_stored >= 2) {
+        out += "l";
+        for (uint32_t k = 0; k < paths[i].n_stored; ++k) out += " " + std::to_string(first + k);
+        out += "\n";
+      }
+      first += paths[i].n_stored;
+    }
+  } else if (type == 1) {
+    out = "ply\nformat ascii 1.0\nelement vertex " + std::to_string(nv) +
+          "\nproperty float x\nproperty float y\nproperty float z\nproperty int step\nelement edge " + std::to_string(ne) +
+          "\nproperty int vertex1\nproperty int vertex2\nend_header\n";
+    for (int64_t i = 0; i < n_paths; ++i)
+      for (uint32_t k = 0; k < paths[i].n_stored; ++k) {
+        const double* v = vert(i, k);
+        std::snprintf(b, sizeof b, "%15.8E %15.8E %15.8E %lld\n", v[0], v[1], v[2], (long long)v[3]);
+        out += b;
+      }
+    int64_t first = 0;  // ply indices are 0-based
+    for (int64_t i = 0; i < n_paths; ++i) {
+      for (uint32_t k = 0; k + 1 < paths[i].n_stored; ++k)
+        out += std::to_string(first + k) + " " + std::to_string(first + k + 1) + "\n";
+      first += paths[i].n_stored;
+    }
+  } else {
+    out = "{\n";
+    for (int64_t i = 0; i < n_paths; ++i) {
+      out += "\"" + std::to_string(paths[i].photon) + "_" + std::to_string(paths[i].hit) + "_" +
+             std::to_string(paths[i].detector) + "\": [\n";
+      for (uint32_t k = 0; k < paths[i].n_stored; ++k) {
+        const double* v = vert(i, k);
+        std::snprintf(b, sizeof b, "[%15.8E,%15.8E,%15.8E]%s\n", v[0], v[1], v[2], k + 1 < paths[i].n_stored ? "," : "");
+        out += b;
+      }
+      out += i + 1 < n_paths ? "],\n" : "]\n";
+    }
+    out += "}\n";
+  }
+  FILE* fp = std::fopen(f.c_str(), "wb");
+  if (!fp) return wfail(SMCRT_ERR_INVALID_ARG, "cannot open " + f);
+  const bool ok = std::fwrite(out.data(), 1, out.size(), fp) == out.size();
+  if (std::fclose(fp) != 0 || !ok) return wfail(SMCRT_ERR_INVALID_ARG, "write failed: " + f);
+  return SMCRT_OK;
+}
+
 }  // extern "C"

@@ -98,6 +98,9 @@ def load_library(path: str = LIB_PATH):
         L.smcrt_multi_device_photons.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         L.smcrt_multi_destroy.argtypes = [C.c_void_p]
         L.smcrt_multi_destroy.restype = None
+        L.smcrt_scene_set_path_tracking.argtypes = [C.c_void_p, C.POINTER(abi.PathConfig)]
+        L.smcrt_scene_path_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4
+        L.smcrt_scene_read_paths.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         if L.smcrt_abi_version() != abi.SMCRT_ABI_VERSION:
             raise SmcrtError("libsmcrt.so ABI version mismatch")
         _lib = L
@@ -274,6 +277,35 @@ class Engine:
         return {"transport_ms": t.transport_ms, "deposit_ms": t.deposit_ms, "launches": t.launches,
                 "lean_launches": t.lean_launches, "far_steps": t.far_steps,
                 "fold_cu_ms": t.fold_cu_ms, "lean_hazards": t.lean_hazards}
+
+    def set_path_tracking(self, range_first=0, range_count=0, max_vertices=64, max_paths=65536):
+        """Configure photon-path recording (smcrt_scene_set_path_tracking): runs made with
+        abi.FLAG_TRACK_PATHS then file the path of every photon of [range_first, range_first +
+        range_count) when it finishes, and the path so far at every hit of a detector built with
+        track_history=True. `set_path_tracking(None)` turns it off and frees the buffers."""
+        if range_first is None:
+            _check(load_library().smcrt_scene_set_path_tracking(self._h, None))
+            return
+        cfg = abi.PathConfig()
+        cfg.range_first, cfg.range_count = int(range_first), int(range_count)
+        cfg.max_vertices, cfg.max_paths = int(max_vertices), int(max_paths)
+        _check(load_library().smcrt_scene_set_path_tracking(self._h, C.byref(cfg)))
+
+    def paths(self):
+        """The paths of the last tracking run (smcrt_scene_read_paths), sorted by (photon, hit):
+        (headers, vertices, counts). `headers` is a structured array (abi.path_dtype()), `vertices`
+        an (n, 4) array of x, y, z, step; path i owns vertices[offset : offset + n_stored].
+        `counts` holds n_paths, n_vertices, n_dropped and n_truncated."""
+        L = load_library()
+        c = [C.c_int64() for _ in range(4)]
+        _check(L.smcrt_scene_path_counts(self._h, *[C.byref(x) for x in c]))
+        counts = dict(zip(("n_paths", "n_vertices", "n_dropped", "n_truncated"), (x.value for x in c)))
+        hdr = np.zeros(counts["n_paths"], dtype=abi.path_dtype())
+        vtx = np.zeros((counts["n_vertices"], 4))
+        if len(hdr):
+            _check(L.smcrt_scene_read_paths(self._h, hdr.ctypes.data_as(C.c_void_p),
+                                            vtx.ctypes.data_as(C.POINTER(C.c_double))))
+        return hdr, vtx, counts
 
     def invoxel_segments(self) -> int:
         """Deposit segments of the scene's finished launches that the lean path's photon waves

@@ -22,6 +22,7 @@ def _lib():
         L.smcrt_job_scene.argtypes = [C.c_void_p, C.POINTER(abi.SdfNode), C.POINTER(C.c_int32),
                                       C.POINTER(abi.Detector)]
         L.smcrt_job_metadata.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+        L.smcrt_job_history_filename.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
         L.smcrt_job_run.argtypes = [C.c_void_p, C.c_int32, C.c_char_p, C.POINTER(C.c_double)]
         L.smcrt_job_load_mode.argtypes = [C.c_char_p, C.c_int32, C.POINTER(C.c_void_p)]
         L.smcrt_job_escape_config.argtypes = [C.c_void_p, C.POINTER(abi.EscapeConfig)]
@@ -80,6 +81,13 @@ class Job:
     def metadata(self) -> str:
         buf = C.create_string_buffer(1 << 16)
         _check(_lib().smcrt_job_metadata(self._h, buf, len(buf)))
+        return buf.value.decode()
+
+    def history_filename(self) -> str:
+        """historyFileName of the first detector with trackHistory = true ("" when none tracks);
+        `run` then writes the photon paths to outdir/<stem>_000<ext>."""
+        buf = C.create_string_buffer(4096)
+        _check(_lib().smcrt_job_history_filename(self._h, buf, len(buf)))
         return buf.value.decode()
 
     def run(self, outdir, device: int = 0) -> float:

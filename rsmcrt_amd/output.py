@@ -28,6 +28,7 @@ def _lib():
                                            C.c_int64]
         L.smcrt_write_checkpoint.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.POINTER(C.c_float),
                                              C.POINTER(abi.Grid), C.c_int32, C.c_char_p, C.c_int32]
+        L.smcrt_write_paths.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double)]
         _declared = True
     return L
 
@@ -74,6 +75,15 @@ def write_checkpoint(filename, toml_filename: str, photons_run: int, jmean, grid
                                          a.ctypes.data_as(C.POINTER(C.c_float)), C.byref(grid),
                                          1 if overwrite else 0, out, len(out)))
     return out.value.decode()
+
+
+def write_paths(filename, headers, vertices) -> None:
+    """The photon paths of Engine.paths() as the reference's history stack writes them
+    (smcrt_write_paths): .obj, .ply or .json by the file's name."""
+    h = np.ascontiguousarray(headers, dtype=abi.path_dtype())
+    v = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 4)
+    _check(_lib().smcrt_write_paths(_b(filename), h.ctypes.data_as(C.c_void_p), len(h),
+                                    v.ctypes.data_as(C.POINTER(C.c_double))))
 
 
 def normalise_fluence(jmean, grid: abi.Grid, nphotons: int) -> np.ndarray:

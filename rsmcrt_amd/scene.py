@@ -478,15 +478,18 @@ DIRECTIONS = {"x": (1.0, 0.0, 0.0), "-x": (-1.0, 0.0, 0.0), "y": (0.0, 1.0, 0.0)
 
 
 # ------------------------------------------------------------------ detectors -----
+# track_history=True on a detector builder (the [[detectors]] key trackHistory): in a run with
+# abi.FLAG_TRACK_PATHS the detector files the photon's path so far at every hit it scores.
 def _norm(v):
     ln = math.sqrt(v[0] ** 2 + v[1] ** 2 + v[2] ** 2)
     return (v[0] / ln, v[1] / ln, v[2] / ln)
 
 
-def circle_dect(pos, direction, layer, radius, nbins) -> abi.Detector:
+def circle_dect(pos, direction, layer, radius, nbins, track_history=False) -> abi.Detector:
     """init_circle_dect, detectors.f90:122-145 (direction normalised by the parser)."""
     d = abi.Detector()
     d.kind = abi.DET_CIRCLE
+    d.reserved = abi.DET_TRACK_HISTORY if track_history else 0
     d.nbins = int(nbins) + 1
     d.layer = int(layer)
     for i in range(3):
@@ -496,10 +499,11 @@ def circle_dect(pos, direction, layer, radius, nbins) -> abi.Detector:
     return d
 
 
-def annulus_dect(pos, direction, layer, r1, r2, nbins) -> abi.Detector:
+def annulus_dect(pos, direction, layer, r1, r2, nbins, track_history=False) -> abi.Detector:
     """init_annulus_dect, detectors.f90:166-200."""
     d = abi.Detector()
     d.kind = abi.DET_ANNULUS
+    d.reserved = abi.DET_TRACK_HISTORY if track_history else 0
     d.nbins = int(nbins) + 1
     d.layer = int(layer)
     for i in range(3):
@@ -509,10 +513,11 @@ def annulus_dect(pos, direction, layer, r1, r2, nbins) -> abi.Detector:
     return d
 
 
-def camera(p1, p2, p3, layer, nbins, maxval) -> abi.Detector:
+def camera(p1, p2, p3, layer, nbins, maxval, track_history=False) -> abi.Detector:
     """init_camera, detectors.f90:401-445: e1=p2-p1, e2=p3-p1, n=normalise(e2 x e1)."""
     d = abi.Detector()
     d.kind = abi.DET_CAMERA
+    d.reserved = abi.DET_TRACK_HISTORY if track_history else 0
     e1 = [float(p2[i]) - float(p1[i]) for i in range(3)]
     e2 = [float(p3[i]) - float(p1[i]) for i in range(3)]
     n = (e2[1] * e1[2] - e2[2] * e1[1], -e2[0] * e1[2] + e2[2] * e1[0], e2[0] * e1[1] - e2[1] * e1[0])
@@ -534,12 +539,13 @@ def camera(p1, p2, p3, layer, nbins, maxval) -> abi.Detector:
 
 def fibre_dect(pos, direction, layer, nbins, focal1=1.0, focal2=1.0, f1_aperture=1.0, f2_aperture=1.0,
                front_offset=0.0, back_offset=None, front_to_pin=None, pin_to_back=None, pin_aperture=None,
-               accept_angle=90.0, core_diameter=0.01) -> abi.Detector:
+               accept_angle=90.0, core_diameter=0.01, track_history=False) -> abi.Detector:
     """init_fibre_dect, detectors.f90:246-329, with the parser's defaults
     (parse_detectors.f90:262-280): back_offset and pin_to_back default to focal2,
     front_to_pin to focal1, pin_aperture to max(f1_aperture, f2_aperture)."""
     d = abi.Detector()
     d.kind = abi.DET_FIBRE
+    d.reserved = abi.DET_TRACK_HISTORY if track_history else 0
     d.nbins = int(nbins) + 1
     d.layer = int(layer)
     direction = _norm(direction)
