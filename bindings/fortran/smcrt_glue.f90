@@ -26,7 +26,7 @@ module smcrt_glue
     public :: smcrt_sphere, smcrt_box, smcrt_torus, smcrt_cylinder, smcrt_triprism, smcrt_segment, &
               smcrt_capsule, smcrt_cone, smcrt_egg, smcrt_plane, smcrt_model
     public :: smcrt_revolution, smcrt_extrude, smcrt_onion, smcrt_twist, smcrt_bend, smcrt_elongate, &
-              smcrt_displacement_sine
+              smcrt_displacement_sine, smcrt_displacement_expr
     public :: smcrt_count_nodes, smcrt_flatten, smcrt_get_vessels
     public :: smcrt_circle_dect, smcrt_annulus_dect, smcrt_camera, smcrt_fibre_dect
     public :: smcrt_source_from
@@ -369,6 +369,19 @@ contains
         type(smcrt_sdf) :: s
         s = modifier(SMCRT_SDF_DISPLACEMENT, prim_sdf, [real(SMCRT_DISP_SINE, c_double), amplitude, freq])
     end function smcrt_displacement_sine
+
+    !> displacement_init (:178-194) with f(p) an arithmetic expression in x, y, z, e.g.
+    !> "0.02*sin(9*x)*cos(7*y)" (smcrt.h "displacement expressions"): smcrt_displacement_compile
+    !> writes the program into the node's transform and param. status: SMCRT_OK, or
+    !> SMCRT_ERR_INVALID_ARG (smcrt_error_message() names the column); s is then unusable.
+    function smcrt_displacement_expr(prim_sdf, expr, status) result(s)
+        type(smcrt_sdf), intent(in) :: prim_sdf
+        character(len=*), intent(in) :: expr
+        integer, intent(out) :: status
+        type(smcrt_sdf) :: s
+        s = modifier(SMCRT_SDF_DISPLACEMENT, prim_sdf, [real(SMCRT_DISP_EXPR, c_double)])
+        status = smcrt_displacement_compile(trim(expr) // c_null_char, s%node)
+    end function smcrt_displacement_expr
 
     ! ------------------------------------------------------------ scene builders ------------
     !> get_vessels (setupGeometry.f90:552-652) for a host that builds the vessel net itself:

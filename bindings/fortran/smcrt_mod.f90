@@ -19,7 +19,7 @@ module smcrt_mod
     ! the modifiers of sdfModifiers.f90 (ABI 4): each wraps one node
     integer(c_int32_t), parameter :: SMCRT_SDF_REVOLUTION = 12, SMCRT_SDF_EXTRUDE = 13, SMCRT_SDF_ONION = 14, &
         SMCRT_SDF_TWIST = 15, SMCRT_SDF_BEND = 16, SMCRT_SDF_ELONGATE = 17, SMCRT_SDF_DISPLACEMENT = 18
-    integer(c_int32_t), parameter :: SMCRT_DISP_SINE = 1
+    integer(c_int32_t), parameter :: SMCRT_DISP_SINE = 1, SMCRT_DISP_EXPR = 2
     integer(c_int), parameter :: SMCRT_MOD_ABI_VERSION = 5  ! compare with smcrt_abi_version()
     ! smcrt_csg_op
     integer(c_int32_t), parameter :: SMCRT_OP_UNION = 0, SMCRT_OP_SMOOTH_UNION = 1, &
@@ -258,6 +258,29 @@ module smcrt_mod
             real(c_double), intent(inout)      :: det_totals(*)
             type(smcrt_tallies), intent(inout) :: io
         end function smcrt_run_origins
+
+        ! displacement expressions (smcrt.h): expr is a NUL-terminated string; the program goes into
+        ! node%transform and node%param, and kind becomes SMCRT_SDF_DISPLACEMENT
+        integer(c_int) function smcrt_displacement_compile(expr, node) bind(C, name="smcrt_displacement_compile")
+            import :: c_int, c_char, smcrt_sdf_node
+            character(kind=c_char), intent(in)  :: expr(*)
+            type(smcrt_sdf_node), intent(inout) :: node
+        end function smcrt_displacement_compile
+
+        integer(c_int) function smcrt_displacement_eval(node, xyz, n, out) bind(C, name="smcrt_displacement_eval")
+            import :: c_int, c_double, c_int64_t, smcrt_sdf_node
+            type(smcrt_sdf_node), intent(in) :: node
+            real(c_double), intent(in)       :: xyz(3, *)
+            integer(c_int64_t), value        :: n
+            real(c_double), intent(out)      :: out(*)
+        end function smcrt_displacement_eval
+
+        integer(c_int) function smcrt_displacement_describe(node, buf, cap) bind(C, name="smcrt_displacement_describe")
+            import :: c_int, c_char, c_int32_t, smcrt_sdf_node
+            type(smcrt_sdf_node), intent(in)     :: node
+            character(kind=c_char), intent(out)  :: buf(*)
+            integer(c_int32_t), value            :: cap
+        end function smcrt_displacement_describe
 
         integer(c_int) function smcrt_scene_classify(scene, points, n, layer, kappa) bind(C, name="smcrt_scene_classify")
             import :: c_int, c_ptr, c_double, c_int64_t, c_int32_t

@@ -74,17 +74,20 @@ typedef enum smcrt_sdf_kind {
                                 (twist_init takes k as default real: pass real(k_sp, wp))      */
   SMCRT_SDF_BEND = 16,       /* param[0]=k: d of p rotated by k*p.x in the xy plane              :373-391 */
   SMCRT_SDF_ELONGATE = 17,   /* param[0..2]=size: q = |p| - size; d(max(q,0)) + min(max(q),0)     :335-351 */
-  SMCRT_SDF_DISPLACEMENT = 18 /* d(p) + f(p) with a built-in f (param[0] = smcrt_displacement_fn):  :393-408
+  SMCRT_SDF_DISPLACEMENT = 18 /* d(p) + f(p), f chosen by param[0] = smcrt_displacement_fn:        :393-408
                                 the reference takes any pure function of pos and ships none    */
 } smcrt_sdf_kind;
 
-/* Built-in displacement functions f(p) of SMCRT_SDF_DISPLACEMENT (param[0]); the reference's
+/* Displacement functions f(p) of SMCRT_SDF_DISPLACEMENT (param[0]); the reference's
  * displacement_init takes an arbitrary procedure(primitive) pointer, which cannot cross to
- * device code. The `repeat` modifier is not provided: its evaluate is an `error stop "Not
- * implmented"` in the reference (sdfModifiers.f90:410-426). */
+ * device code: f is the built-in sine product or an arithmetic expression in x, y, z compiled
+ * into the node (see "displacement expressions" below). The `repeat` modifier is not provided:
+ * its evaluate is an `error stop "Not implmented"` in the reference (sdfModifiers.f90:410-426). */
 typedef enum smcrt_displacement_fn {
-  SMCRT_DISP_SINE = 1 /* param[1]=amplitude a, param[2..4]=frequencies (fx, fy, fz):
-                         f(p) = ((a * sin(fx*p.x)) * sin(fy*p.y)) * sin(fz*p.z) */
+  SMCRT_DISP_SINE = 1, /* param[1]=amplitude a, param[2..4]=frequencies (fx, fy, fz):
+                          f(p) = ((a * sin(fx*p.x)) * sin(fy*p.y)) * sin(fz*p.z) */
+  SMCRT_DISP_EXPR = 2  /* f(p) = the postfix program stored in transform[] and param[1..10],
+                          written by smcrt_displacement_compile */
 } smcrt_displacement_fn;
 
 /* CSG operators of a MODEL node (sdfModifiers.f90:428-491). */
@@ -334,6 +337,50 @@ int smcrt_scene_det_bins(const smcrt_scene* scene, int64_t* n_doubles);
  * sdf_base.f90:255-263; used by inverse MCRT). */
 int smcrt_scene_set_optprops(smcrt_scene* scene, int32_t top_index,
                              double mus, double mua, double hgg, double n);
+
+/* ---- displacement expressions (SMCRT_DISP_EXPR) ---------------------------------------------
+ * f(p) of a displacement node as an expression in the point the modifier is evaluated at:
+ *   expr    := term (('+' | '-') term)*              left-associative
+ *   term    := unary (('*' | '/') unary)*            left-associative
+ *   unary   := '-' unary | primary
+ *   primary := number | 'x' | 'y' | 'z' | 'pi' | '(' expr ')' | f1 '(' expr ')' | f2 '(' expr ',' expr ')'
+ *   f1      := abs | sqrt | sin | cos | floor        f2 := min | max
+ * Numbers are decimal literals as strtod reads them (1.5, .25, 1e-3), so a value printed with
+ * 17 significant digits comes back bit for bit. The program performs exactly the fp64
+ * operations written, in the order written: nothing is rewritten or re-associated; the only
+ * folding is '-' directly before a number, which is that number negated. + - * / sqrt floor
+ * are the IEEE operations (the library is built without contraction), min(a,b) = a < b ? a : b,
+ * max(a,b) = a > b ? a : b, and sin/cos are the engine's own, bit-identical on host and device.
+ * There is no pow, exp or log.
+ *
+ * Encoding. The program lives in the fields a modifier never uses; the node is self-contained
+ * and can be copied, stored and sent like any other:
+ *   param[0]           SMCRT_DISP_EXPR
+ *   param[1]           number of instructions, 1..64
+ *   param[2]           number of constants, 0..12
+ *   param[3..10]       the code: 64 bytes, instruction i in byte i (byte 0 is the lowest byte of
+ *                      param[3]'s bit pattern); bytes after the last instruction are 0
+ *   param[11]          0
+ *   transform[0..11]   the constants (distinct bit patterns); transform[12..15] and unused slots 0
+ * Opcodes: 1, 2, 3 push x, y, z; 16 + i pushes constant i; 4..9 pop b, pop a, push a+b, a-b,
+ * a*b, a/b, min(a,b), max(a,b); 10..15 replace the top by -a, abs, sqrt, sin, cos, floor. The
+ * program is postfix, leaves exactly one value, and never holds more than 8 values on its
+ * stack. Every opcode is below 64, so no code double is a NaN or an infinity.
+ * smcrt_scene_create verifies all of this and answers SMCRT_ERR_INVALID_ARG to a node that
+ * breaks it, before any device call. */
+
+/* Compile `expr` into `node`: sets kind = SMCRT_SDF_DISPLACEMENT, transform[] and param[] as
+ * above; layer, optics, first_child and n_children stay the caller's. An error (syntax, an
+ * unknown name, more than 64 instructions, 12 constants or 8 stack values) is
+ * SMCRT_ERR_INVALID_ARG, smcrt_last_error() names the 1-based character column, and `node` is
+ * left unchanged. */
+int smcrt_displacement_compile(const char* expr, smcrt_sdf_node* node);
+/* out[i] = f(xyz[3i], xyz[3i+1], xyz[3i+2]) for i < n, by the interpreter the kernels run, on
+ * the host; needs no device. `node` must hold a valid program. */
+int smcrt_displacement_eval(const smcrt_sdf_node* node, const double* xyz, int64_t n, double* out);
+/* The node's program as a fully parenthesised expression (NUL-terminated, at most cap bytes
+ * with the NUL); compiling it yields the same transform[] and param[]. */
+int smcrt_displacement_describe(const smcrt_sdf_node* node, char* buf, int32_t cap);
 
 /* ---- ABI 5: spectral optical properties (opticalProperties.f90:127-201) -------------------
  * The reference's `spectral` type holds five piecewise1D tables (init_piecewise1D,

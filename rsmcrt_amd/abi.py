@@ -28,7 +28,7 @@ SDF_SPHERE, SDF_BOX, SDF_TORUS, SDF_CYLINDER, SDF_TRIPRISM = 1, 2, 3, 4, 5
 SDF_SEGMENT, SDF_CAPSULE, SDF_CONE, SDF_EGG, SDF_PLANE, SDF_MODEL = 6, 7, 8, 9, 10, 11
 # the modifiers of src/sdfs/sdfModifiers.f90 (ABI 4): each wraps one node
 SDF_REVOLUTION, SDF_EXTRUDE, SDF_ONION, SDF_TWIST, SDF_BEND, SDF_ELONGATE, SDF_DISPLACEMENT = 12, 13, 14, 15, 16, 17, 18
-DISP_SINE = 1  # smcrt_displacement_fn
+DISP_SINE, DISP_EXPR = 1, 2  # smcrt_displacement_fn (DISP_EXPR: scene.displacement)
 
 # smcrt_csg_op (src/sdfs/sdfModifiers.f90:428-491)
 OP_UNION, OP_SMOOTH_UNION, OP_SUBTRACTION, OP_INTERSECTION = 0, 1, 2, 3
@@ -263,4 +263,5 @@ EXPORTED_SYMBOLS = [
     "smcrt_scene_invoxel_segments",
     "smcrt_scene_set_path_tracking", "smcrt_scene_path_counts", "smcrt_scene_read_paths", "smcrt_write_paths",
     "smcrt_job_history_filename",
+    "smcrt_displacement_compile", "smcrt_displacement_eval", "smcrt_displacement_describe",
 ]

@@ -19,7 +19,7 @@ from concurrent.futures import ThreadPoolExecutor
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB = os.path.join(PKG, "libsmcrt.so")
-SOURCES = [os.path.join(PKG, "csrc", f) for f in ("smcrt.hip", "writers.cpp", "frontend.cpp", "sources.cpp", "png.cpp", "escape.cpp", "inverse.cpp", "spectral.cpp", "multi.hip", "cull.cpp", "sceneplan.cpp")]
+SOURCES = [os.path.join(PKG, "csrc", f) for f in ("smcrt.hip", "writers.cpp", "frontend.cpp", "sources.cpp", "png.cpp", "escape.cpp", "inverse.cpp", "spectral.cpp", "multi.hip", "cull.cpp", "sceneplan.cpp", "dispexpr.cpp")]
 # the transport kernel instantiations: kinst.hip once per (LDS faces, grid mode), kernel_ptrs.h
 KINST = os.path.join(PKG, "csrc", "kinst.hip")
 # Part 1 (the plain ws_kernel, M1's lean path) schedules with the AMDGPU register-pressure

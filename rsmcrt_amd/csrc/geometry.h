@@ -218,9 +218,99 @@ __host__ __device__ __forceinline__ V3 modifier_point(const smcrt_sdf_node* __re
   }
 }
 
-// A modifier's value from its wrapped node's value d at its own query point pos.
-// Extrude :286-301, onion :323-333, elongate :335-351 (+ w), displacement :393-408.
-__host__ __device__ __forceinline__ double modifier_value(const smcrt_sdf_node* __restrict__ M, double d, V3 pos) {
+// SMCRT_DISP_EXPR: a displacement's f(p) as a postfix byte program kept in the node itself
+// (smcrt.h "displacement expressions" has the encoding; dispexpr.h compiles and verifies it).
+// One byte per instruction, every opcode below 64, so that none of the eight doubles that hold
+// the code is a NaN or an infinity whatever the program.
+enum : uint32_t {
+  DX_END = 0,                                                      // (padding after the last instruction)
+  DX_X = 1, DX_Y = 2, DX_Z = 3,                                    // push a coordinate of pos
+  DX_ADD = 4, DX_SUB = 5, DX_MUL = 6, DX_DIV = 7, DX_MIN = 8, DX_MAX = 9,  // a b -> a op b
+  DX_NEG = 10, DX_ABS = 11, DX_SQRT = 12, DX_SIN = 13, DX_COS = 14, DX_FLOOR = 15,  // a -> f(a)
+  DX_CONST = 16,                                                   // DX_CONST + i: push transform[i]
+};
+constexpr int DX_MAX_CODE = 64;    // instructions: the bytes of param[DX_CODE_PARAM .. +7]
+constexpr int DX_MAX_CONSTS = 12;  // constants: transform[0..11]
+constexpr int DX_MAX_STACK = 8;    // values on the evaluation stack (checked when compiled and verified)
+constexpr int DX_LEN_PARAM = 1, DX_NCONST_PARAM = 2, DX_CODE_PARAM = 3;
+typedef uint64_t __attribute__((may_alias)) dx_word;
+
+// The program of node M at pos, M the same for every lane that calls: its words are read eight
+// instructions at a time and the switch is on a value every lane shares. The stack pointer is
+// masked, the constant index is bounded by its opcode range and the loop ends with the node's
+// 64 code bytes, so nothing outside the node (or the stack) is touched whatever the words hold.
+__host__ __device__ __forceinline__ double disp_expr_run(const smcrt_sdf_node* __restrict__ M, V3 pos) {
+  const dx_word* __restrict__ code = reinterpret_cast<const dx_word*>(M->param + DX_CODE_PARAM);
+  double st[DX_MAX_STACK];  // st[1..7] below the top of the stack t (st[0] takes the first push's spill)
+  double t = 0.0;
+  uint32_t sp = 0;
+#pragma unroll 1
+  for (int w = 0; w < DX_MAX_CODE / 8; ++w) {
+    dx_word word = code[w];
+#pragma unroll 1
+    for (int b = 0; b < 8; ++b, word >>= 8) {
+      const uint32_t op = (uint32_t)word & 0xFFu;
+      if (op == DX_END) return t;
+      if (op < DX_ADD || op >= DX_CONST) {  // a push
+        st[sp & (DX_MAX_STACK - 1)] = t;
+        ++sp;
+        t = op == DX_X ? pos.x : op == DX_Y ? pos.y : op == DX_Z ? pos.z
+            : op < DX_CONST + DX_MAX_CONSTS ? M->transform[op - DX_CONST] : __builtin_nan("");
+      } else if (op < DX_NEG) {
+        --sp;
+        const double a = st[sp & (DX_MAX_STACK - 1)];
+        switch (op) {
+          case DX_ADD: t = a + t; break;
+          case DX_SUB: t = a - t; break;
+          case DX_MUL: t = a * t; break;
+          case DX_DIV: t = a / t; break;
+          case DX_MIN: t = dmin(a, t); break;
+          default: t = dmax(a, t); break;
+        }
+      } else {
+        switch (op) {
+          case DX_NEG: t = -t; break;
+          case DX_ABS: t = fabs(t); break;
+          case DX_SQRT: t = sqrt(t); break;
+          case DX_FLOOR: t = floor(t); break;
+          default: {  // DX_SIN, DX_COS: one inlined copy of det_sincos_any for both
+            double sn, cs;
+            det_sincos_any(t, &sn, &cs);
+            t = op == DX_SIN ? sn : cs;
+          }
+        }
+      }
+    }
+  }
+  return t;
+}
+
+// f(pos) of displacement node `idx`. On the device the lanes of a wave may hold different nodes
+// (the cooperative EVALs give each lane a top of its own), so the wave takes its distinct
+// nodes in turn: each turn's index is the first live lane's, held in a scalar register, which
+// makes the program words scalar loads and the opcode branches uniform.
+__host__ __device__ __forceinline__ double disp_expr_value(const smcrt_sdf_node* __restrict__ nodes, int32_t idx, V3 pos) {
+#ifdef __HIP_DEVICE_COMPILE__
+  double v = 0.0;
+  for (bool done = false; !done;) {
+    if (__builtin_amdgcn_readfirstlane(idx) == idx) {
+      // (taken again among the lanes that agree: the compiler may replace the value compared
+      // above by the lane's own idx, which it does not know to be uniform)
+      v = disp_expr_run(nodes + __builtin_amdgcn_readfirstlane(idx), pos);
+      done = true;
+    }
+  }
+  return v;
+#else
+  return disp_expr_run(nodes + idx, pos);
+#endif
+}
+
+// A modifier's value from its wrapped node's value d at its own query point pos; the modifier
+// is nodes[idx]. Extrude :286-301, onion :323-333, elongate :335-351 (+ w), displacement :393-408.
+__host__ __device__ __forceinline__ double modifier_value(const smcrt_sdf_node* __restrict__ nodes, int32_t idx, double d,
+                                                          V3 pos) {
+  const smcrt_sdf_node* __restrict__ M = nodes + idx;
   const double* P = M->param;
   switch (M->kind) {
     case SMCRT_SDF_EXTRUDE: {  // w = (d, abs(pos%z) - h, 0); min(max(w%x, w%y), 0) + length(max(w, 0))
@@ -233,7 +323,8 @@ __host__ __device__ __forceinline__ double modifier_value(const smcrt_sdf_node* 
       const V3 q = vabs(pos) - v3(P[0], P[1], P[2]);
       return d + dmin(dmax(q.x, dmax(q.y, q.z)), 0.0);
     }
-    case SMCRT_SDF_DISPLACEMENT: {  // d1 + d2, d2 = the built-in f(pos) (smcrt.h smcrt_displacement_fn)
+    case SMCRT_SDF_DISPLACEMENT: {  // d1 + d2, d2 = f(pos) (smcrt.h smcrt_displacement_fn)
+      if (P[0] == (double)SMCRT_DISP_EXPR) return d + disp_expr_value(nodes, idx, pos);
       double sx, sy, sz, c;
       det_sincos_any(P[2] * pos.x, &sx, &c);
       det_sincos_any(P[3] * pos.y, &sy, &c);
@@ -280,7 +371,7 @@ __host__ __device__ __forceinline__ double node_value(const smcrt_sdf_node* __re
       }
       v = sdf_prim(nodes + ci, q, false);  // a primitive child: folded into this frame
     } else {  // every child folded: the composite's value goes to its parent frame
-      v = model ? st[sp].acc : modifier_value(M, st[sp].acc, st[sp].pos);
+      v = model ? st[sp].acc : modifier_value(nodes, st[sp].idx, st[sp].acc, st[sp].pos);
       if (sp == 0) return v;
       --sp;
     }

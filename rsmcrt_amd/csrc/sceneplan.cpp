@@ -9,6 +9,7 @@
 #include <functional>
 #include <string>
 
+#include "dispexpr.h"
 #include "hosterr.h"
 
 namespace smcrt {
@@ -122,8 +123,13 @@ int validate(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top, i
     } else if (composite_kind(nd.kind)) {  // a modifier wraps exactly one node
       if (nd.n_children != 1 || nd.first_child < 0 || nd.first_child >= n_nodes)
         return fail(SMCRT_ERR_INVALID_ARG, "modifier node " + std::to_string(i) + ": needs exactly one child");
-      if (nd.kind == SMCRT_SDF_DISPLACEMENT && nd.param[0] != (double)SMCRT_DISP_SINE)
+      if (nd.kind == SMCRT_SDF_DISPLACEMENT && nd.param[0] == (double)SMCRT_DISP_EXPR) {
+        std::string why;  // the stored program, before the device interprets it (dispexpr.h)
+        if (!disp_expr_verify(nd, &why))
+          return fail(SMCRT_ERR_INVALID_ARG, "displacement node " + std::to_string(i) + ": bad expression program: " + why);
+      } else if (nd.kind == SMCRT_SDF_DISPLACEMENT && nd.param[0] != (double)SMCRT_DISP_SINE) {
         return fail(SMCRT_ERR_INVALID_ARG, "displacement node " + std::to_string(i) + ": unknown function");
+      }
     }
   }
   // models and modifiers nested at most PROG_MAX_DEPTH levels (geometry.h node_value); this

@@ -101,6 +101,10 @@ def load_library(path: str = LIB_PATH):
         L.smcrt_scene_set_path_tracking.argtypes = [C.c_void_p, C.POINTER(abi.PathConfig)]
         L.smcrt_scene_path_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4
         L.smcrt_scene_read_paths.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.smcrt_displacement_compile.argtypes = [C.c_char_p, C.POINTER(abi.SdfNode)]
+        L.smcrt_displacement_eval.argtypes = [C.POINTER(abi.SdfNode), C.POINTER(C.c_double), C.c_int64,
+                                              C.POINTER(C.c_double)]
+        L.smcrt_displacement_describe.argtypes = [C.POINTER(abi.SdfNode), C.c_char_p, C.c_int32]
         if L.smcrt_abi_version() != abi.SMCRT_ABI_VERSION:
             raise SmcrtError("libsmcrt.so ABI version mismatch")
         _lib = L

@@ -237,6 +237,9 @@ class Modifier:
     kind: int
     child: object
     param: List[float]
+    # the node's transform[16] and param[12] as raw bytes (a compiled displacement expression,
+    # which lives in those fields: smcrt.h), written in place of the identity and `param`
+    words: Optional[bytes] = None
 
     @property
     def opt(self) -> Mono:
@@ -284,6 +287,62 @@ def displacement_sine(prim, amplitude, freq: Vec) -> Modifier:
     return Modifier(abi.SDF_DISPLACEMENT, prim, [float(abi.DISP_SINE), float(amplitude), *map(float, freq)])
 
 
+_WORDS_OFFSET = abi.SdfNode.transform.offset
+_WORDS_SIZE = abi.SdfNode.transform.size + abi.SdfNode.param.size
+assert abi.SdfNode.param.offset == _WORDS_OFFSET + abi.SdfNode.transform.size
+
+
+def _program_node(words: bytes) -> abi.SdfNode:
+    nd = abi.SdfNode()
+    nd.kind = abi.SDF_DISPLACEMENT
+    assert len(words) == _WORDS_SIZE
+    C.memmove(C.addressof(nd) + _WORDS_OFFSET, words, _WORDS_SIZE)
+    return nd
+
+
+def displacement(prim, expr: str) -> Modifier:
+    """displacement_init(prim, func) :178-194 with f(p) an arithmetic expression in x, y, z
+    (+ - * / and unary minus, parentheses, pi, abs sqrt sin cos floor min max; smcrt.h
+    "displacement expressions"), compiled by smcrt_displacement_compile into the words the node
+    carries. Raises ValueError with the library's message (it names the column) if `expr` does
+    not compile. The sphere trace needs |grad f| well below 1, as in the reference."""
+    from .engine import load_library
+    L = load_library()
+    nd = abi.SdfNode()
+    if L.smcrt_displacement_compile(str(expr).encode(), C.byref(nd)) != abi.OK:
+        raise ValueError(L.smcrt_last_error().decode(errors="replace"))
+    words = C.string_at(C.addressof(nd) + _WORDS_OFFSET, _WORDS_SIZE)
+    return Modifier(abi.SDF_DISPLACEMENT, prim, [nd.param[i] for i in range(12)], words)
+
+
+def implicit(expr: str, opt, layer) -> Modifier:
+    """An SDF given by a formula: `expr` displacing a plane whose normal is (0, 0, 0). The
+    plane's value is +-0 everywhere and +-0 + v == v, so the top's value is the expression's."""
+    return displacement(plane((0.0, 0.0, 0.0), opt, layer), expr)
+
+
+def displacement_eval(mod: Modifier, pts) -> "np.ndarray":
+    """f(p) of a displacement(...) modifier at pts (n, 3): smcrt_displacement_eval, the kernels'
+    interpreter run on the host (no device needed)."""
+    from .engine import load_library, _check
+    pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
+    out = np.empty(len(pts))
+    nd = _program_node(mod.words)
+    dp = C.POINTER(C.c_double)
+    _check(load_library().smcrt_displacement_eval(C.byref(nd), pts.ctypes.data_as(dp), len(pts), out.ctypes.data_as(dp)))
+    return out
+
+
+def displacement_describe(mod: Modifier) -> str:
+    """The program of a displacement(...) modifier as a fully parenthesised expression, which
+    compiles to the same words (smcrt_displacement_describe)."""
+    from .engine import load_library, _check
+    buf = C.create_string_buffer(8192)
+    nd = _program_node(mod.words)
+    _check(load_library().smcrt_displacement_describe(C.byref(nd), buf, len(buf)))
+    return buf.value.decode()
+
+
 class Scene:
     """An ordered sdfs_array (reference index i+1 == tauint2 layer) flattened to nodes."""
 
@@ -306,6 +365,9 @@ class Scene:
                     nd.transform[i] = v
                 for i, v in enumerate(s.param):
                     nd.param[i] = float(v)
+                if s.words is not None:
+                    assert len(s.words) == _WORDS_SIZE
+                    C.memmove(C.addressof(nd) + _WORDS_OFFSET, s.words, _WORDS_SIZE)
                 _set_opt(nd, s.opt)
                 nd.first_child = len(nodes)
                 nd.n_children = 1
