@@ -40,6 +40,8 @@ module smcrt_mod
     integer(c_int32_t), parameter :: SMCRT_FLAG_PATHLENGTH = 1, SMCRT_FLAG_SURVIVAL_BIAS = 2, &
         SMCRT_FLAG_RENDER_SOURCE = 4, SMCRT_FLAG_TEST_KERNEL = 8, SMCRT_FLAG_END_EARLY = 16, &
         SMCRT_FLAG_RECORD_PHOTONS = 32, SMCRT_FLAG_ASYNC_FOLD = 64, SMCRT_FLAG_OVERLAP = 128
+    ! smcrt_run only, on a scene configured with smcrt_scene_set_phasor: the complex phasor grid
+    integer(c_int32_t), parameter :: SMCRT_FLAG_PHASOR = 512
     integer, parameter :: SMCRT_NCOUNTERS = 16
     ! multi-GPU: packed-tally fields (smcrt_pack_layout%fields), all visible devices
     integer(c_int32_t), parameter :: SMCRT_PACK_JMEAN = 1, SMCRT_PACK_ABSORB = 2, SMCRT_PACK_EMISSION = 4, &
@@ -157,6 +159,11 @@ module smcrt_mod
         integer(c_int64_t) :: lean_hazards = 0  ! ABI 4
     end type smcrt_kernel_times
 
+    type, bind(C) :: smcrt_phasor_config          ! the phasor tally (smcrt.h "phasor tally")
+        integer(c_int32_t) :: fixed_k = 0, reserved = 0
+        real(c_double)     :: wavenumber = 0._c_double  ! with fixed_k /= 0: every photon's k
+    end type smcrt_phasor_config
+
     interface
         integer(c_int) function smcrt_abi_version() bind(C, name="smcrt_abi_version")
             import :: c_int
@@ -202,6 +209,24 @@ module smcrt_mod
             integer(c_int32_t), value :: top_index
             real(c_double), value     :: mus, mua, hgg, n
         end function smcrt_scene_set_optprops
+
+        ! cfg: c_loc of a smcrt_phasor_config (target), or c_null_ptr to turn the tally off
+        integer(c_int) function smcrt_scene_set_phasor(scene, cfg) bind(C, name="smcrt_scene_set_phasor")
+            import :: c_int, c_ptr
+            type(c_ptr), value :: scene, cfg
+        end function smcrt_scene_set_phasor
+
+        ! adds the grid into phasor(nx, ny, nz) (complex(c_double_complex): re, im interleaved)
+        integer(c_int) function smcrt_scene_read_phasor(scene, phasor) bind(C, name="smcrt_scene_read_phasor")
+            import :: c_int, c_ptr, c_double_complex
+            type(c_ptr), value                        :: scene
+            complex(c_double_complex), intent(inout)  :: phasor(*)
+        end function smcrt_scene_read_phasor
+
+        integer(c_int) function smcrt_scene_reset_phasor(scene) bind(C, name="smcrt_scene_reset_phasor")
+            import :: c_int, c_ptr
+            type(c_ptr), value :: scene
+        end function smcrt_scene_reset_phasor
 
         integer(c_int) function smcrt_scene_check(scene) bind(C, name="smcrt_scene_check")
             import :: c_int, c_ptr

@@ -243,8 +243,10 @@ enum {
                                           fills the GPU while launch k's slowest photons finish; every
                                           tally is complete in `stream` order only after
                                           smcrt_scene_fence (implies SMCRT_FLAG_ASYNC_FOLD) */
-  SMCRT_FLAG_TRACK_PATHS = 1u << 8     /* smcrt_run only: record photon paths into the arena configured with
+  SMCRT_FLAG_TRACK_PATHS = 1u << 8,    /* smcrt_run only: record photon paths into the arena configured with
                                           smcrt_scene_set_path_tracking (see "photon paths" below) */
+  SMCRT_FLAG_PHASOR = 1u << 9          /* smcrt_run only: accumulate the complex phasor grid configured with
+                                          smcrt_scene_set_phasor (see "phasor tally" below) */
 };
 
 typedef struct smcrt_run_config {
@@ -487,6 +489,44 @@ int smcrt_scene_path_counts(smcrt_scene* scene, int64_t* n_paths, int64_t* n_ver
 /* The n_paths records sorted by (photon, hit), and their n_vertices stored vertices (4 doubles
  * each: x, y, z, step) in the same order; paths[i].offset is path i's first vertex. */
 int smcrt_scene_read_paths(smcrt_scene* scene, smcrt_path* paths, double* vertices /* 4 per stored vertex */);
+
+/* ---- phasor tally (the reference's phase tracking: photon%phase, photon%fact, iarray phasor) --
+ * The reference gives every packet a phase and fact = 2 pi / wavelength, adds each voxel piece
+ * of update_grids to the phase (inttau2.f90:425,432) and allocates, zeroes and reduces a
+ * phasor(nx, ny, nz) grid, but never accumulates into it. The definition is therefore this
+ * library's:
+ *  - phase (a length) is set at every emission: dslit and aperture start with the distance from
+ *    the sampled aperture point to the emission point (photon.f90:755,823), every other source
+ *    with 0;
+ *  - k is 2 pi / the wavelength the source's spectrum sampled for that emission (slm, whose
+ *    spectrum is an image, keeps the reference's 500e-9), or `wavenumber` with fixed_k;
+ *  - every voxel piece of update_grids adds its fp64 length to the phase;
+ *  - a piece that ends on a voxel wall (the grid's outer walls included) then adds
+ *    weight * (cos(k * phase), sin(k * phase)) to the voxel it leaves. Pieces that end inside a
+ *    voxel, where the sphere trace happened to stop, are not sampled, so the tally does not
+ *    depend on the step pattern. cos and sin are the engine's own, bit-identical on host and
+ *    device.
+ * The grid is fp64, (re, im) interleaved: 2 * nx * ny * nz doubles, voxels in jmean's order. It
+ * lives on the scene's device, accumulates over runs and is summed with atomics, so its low bits
+ * depend on the order of the sums. SMCRT_FLAG_PHASOR needs SMCRT_FLAG_PATHLENGTH (the tally
+ * lives in the voxel walk) and a configured scene (else SMCRT_ERR_INVALID_ARG); together with
+ * SMCRT_FLAG_TRACK_PATHS it is SMCRT_ERR_UNSUPPORTED. It is accepted by smcrt_run only: every
+ * other driver (smcrt_run_device, smcrt_run_origins, the escape and inverse drivers,
+ * smcrt_multi_*) answers SMCRT_ERR_INVALID_ARG, and smcrt_job_* never sets it. Every other tally
+ * of a phasor run is that of the same run without the flag. */
+typedef struct smcrt_phasor_config {
+  int32_t fixed_k;   /* != 0: every photon's k is `wavenumber` */
+  int32_t reserved;
+  double wavenumber; /* with fixed_k: finite and >= 0 (0 makes the tally a real crossing count) */
+} smcrt_phasor_config;
+
+/* Configure (allocating and zeroing the grid) or, with cfg NULL, turn off and free the phasor
+ * tally of a scene. SMCRT_ERR_OOM if the grid does not fit. */
+int smcrt_scene_set_phasor(smcrt_scene* scene, const smcrt_phasor_config* cfg);
+/* Wait for the scene's runs and ADD the grid into out[2 * nx*ny*nz]. */
+int smcrt_scene_read_phasor(smcrt_scene* scene, double* out);
+/* Zero the grid. */
+int smcrt_scene_reset_phasor(smcrt_scene* scene);
 
 /* Device-resident variant for multi-GPU and benchmarking: launches on `stream`
  * (a hipStream_t; NULL = the legacy default stream) and accumulates into caller-owned

@@ -61,6 +61,7 @@ FLAG_RECORD_PHOTONS = 1 << 5
 FLAG_ASYNC_FOLD = 1 << 6
 FLAG_OVERLAP = 1 << 7
 FLAG_TRACK_PATHS = 1 << 8  # smcrt_run only: record photon paths (Engine.set_path_tracking)
+FLAG_PHASOR = 1 << 9  # smcrt_run only: accumulate the complex phasor grid (Engine.set_phasor)
 
 # smcrt_detector.reserved, bit 0: the detector files the photon's path at every hit it scores
 DET_TRACK_HISTORY = 1
@@ -182,6 +183,10 @@ class Path(C.Structure):
                 ("start", C.c_double * 3), ("dir", C.c_double * 3), ("point_sep", C.c_double), ("weight", C.c_double)]
 
 
+class PhasorConfig(C.Structure):
+    _fields_ = [("fixed_k", C.c_int32), ("reserved", C.c_int32), ("wavenumber", C.c_double)]
+
+
 # smcrt_path as a numpy dtype (same layout)
 def path_dtype():
     import numpy as np
@@ -263,5 +268,6 @@ EXPORTED_SYMBOLS = [
     "smcrt_scene_invoxel_segments",
     "smcrt_scene_set_path_tracking", "smcrt_scene_path_counts", "smcrt_scene_read_paths", "smcrt_write_paths",
     "smcrt_job_history_filename",
+    "smcrt_scene_set_phasor", "smcrt_scene_read_phasor", "smcrt_scene_reset_phasor",
     "smcrt_displacement_compile", "smcrt_displacement_eval", "smcrt_displacement_describe",
 ]

@@ -486,6 +486,8 @@ int smcrt_escape_run(smcrt_scene* scene, const smcrt_source* src, const smcrt_es
   if (!scene || !run || !io) return set_error(SMCRT_ERR_INVALID_ARG, "NULL argument");
   if (run->flags & SMCRT_FLAG_TRACK_PATHS)
     return set_error(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
+  if (run->flags & SMCRT_FLAG_PHASOR)
+    return set_error(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PHASOR: the phasor grid is tallied by smcrt_run only");
   smcrt_grid g;
   int32_t nd = 0;
   if ((st = smcrt_scene_info(scene, &g, nullptr, &nd))) return st;

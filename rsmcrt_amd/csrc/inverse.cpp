@@ -28,6 +28,8 @@ int smcrt_inverse_run(smcrt_scene* scene, const smcrt_source* src, const smcrt_i
   if (cfg->max_steps < 1) return set_error(SMCRT_ERR_INVALID_ARG, "maxNumSteps must be >= 1");
   if (run->flags & SMCRT_FLAG_TRACK_PATHS)
     return set_error(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
+  if (run->flags & SMCRT_FLAG_PHASOR)
+    return set_error(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PHASOR: the phasor grid is tallied by smcrt_run only");
   if (run->n_photons == 0) return set_error(SMCRT_ERR_INVALID_ARG, "n_photons must be > 0");
   const bool fmus = cfg->flags & SMCRT_INVERSE_FIND_MUS, fmua = cfg->flags & SMCRT_INVERSE_FIND_MUA,
              fg = cfg->flags & SMCRT_INVERSE_FIND_G, fn = cfg->flags & SMCRT_INVERSE_FIND_N;

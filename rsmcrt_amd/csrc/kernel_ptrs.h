@@ -2,7 +2,8 @@
 //
 // build.py compiles kinst.hip once per (LDS faces F, grid mode G, part P) with -DKI_F=F -DKI_G=G
 // -DKI_P=P (part 1: the plain ws_kernel, with its own scheduler flags; part 2, F = 0 only:
-// transport_kernel's HIST instantiations, the photon path recorder of paths.h), so
+// transport_kernel's HIST instantiations, the photon path recorder of paths.h; part 3, F = 0
+// only: its PHAS instantiations, the phasor tally of phasor.h), so
 // the instantiations of transport_kernel and ws_kernel (kernels.h, ws.h) build in parallel
 // instead of in one translation unit. Each object exports these getters; hipLaunchKernel and
 // the occupancy queries take the host stubs they return.
@@ -36,12 +37,24 @@ SMCRT_KINST_HIST_DECL(0)
 SMCRT_KINST_HIST_DECL(1)
 SMCRT_KINST_HIST_DECL(2)
 #undef SMCRT_KINST_HIST_DECL
+#define SMCRT_KINST_PHAS_DECL(G)                                  \
+  const void* kinst_transport_phas_0_##G(int xsrc, int coop);     \
+  void kinst_diagf_0_##G(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6);
+SMCRT_KINST_PHAS_DECL(0)
+SMCRT_KINST_PHAS_DECL(1)
+SMCRT_KINST_PHAS_DECL(2)
+#undef SMCRT_KINST_PHAS_DECL
 
-// transport_kernel<lds_faces, gm, xsrc, coop, hist>; the general emitter with the COOP machinery
-// (xsrc && coop) and the path recorder (hist, paths.h) exist with faces in device memory only
-inline const void* transport_kernel_ptr(bool lds_faces, int gm, bool xsrc, bool coop, bool hist = false) {
-  if ((xsrc && coop) || hist) lds_faces = false;
+// transport_kernel<lds_faces, gm, xsrc, coop, hist, phas>; the general emitter with the COOP
+// machinery (xsrc && coop), the path recorder (hist, paths.h) and the phasor tally (phas,
+// phasor.h) exist with faces in device memory only; hist && phas does not exist (nullptr)
+inline const void* transport_kernel_ptr(bool lds_faces, int gm, bool xsrc, bool coop, bool hist = false,
+                                        bool phas = false) {
+  if ((xsrc && coop) || hist || phas) lds_faces = false;
   const int x = xsrc ? 1 : 0, c = coop ? 1 : 0;
+  if (hist && phas) return nullptr;
+  if (phas) return gm == 0 ? kinst_transport_phas_0_0(x, c) : gm == 1 ? kinst_transport_phas_0_1(x, c)
+                                                                      : kinst_transport_phas_0_2(x, c);
   if (hist) return gm == 0 ? kinst_transport_hist_0_0(x, c) : gm == 1 ? kinst_transport_hist_0_1(x, c)
                                                                       : kinst_transport_hist_0_2(x, c);
   switch ((lds_faces ? 3 : 0) + gm) {
@@ -76,6 +89,7 @@ inline void kinst_diag_gather(unsigned long long* d72, unsigned long long* t9, u
   kinst_diagp_0_0(d72, t9, c6); kinst_diagp_0_1(d72, t9, c6); kinst_diagp_0_2(d72, t9, c6);
   kinst_diagp_1_0(d72, t9, c6); kinst_diagp_1_1(d72, t9, c6); kinst_diagp_1_2(d72, t9, c6);
   kinst_diagh_0_0(d72, t9, c6); kinst_diagh_0_1(d72, t9, c6); kinst_diagh_0_2(d72, t9, c6);
+  kinst_diagf_0_0(d72, t9, c6); kinst_diagf_0_1(d72, t9, c6); kinst_diagf_0_2(d72, t9, c6);
 }
 
 }  // namespace smcrt

@@ -11,6 +11,7 @@
 #include "transport.h"
 #include "deposit.h"
 #include "paths.h"
+#include "phasor.h"
 
 using namespace smcrt;
 // ------------------------------------------------------------------ kernel ---------
@@ -83,7 +84,12 @@ constexpr int SOLO_LANES = SMCRT_SOLO_LANES;
 #endif
 // HIST: the photon path recorder (paths.h, SMCRT_FLAG_TRACK_PATHS). Every line of it is under
 // `if constexpr (HIST)`, so the other instantiations are what they were without it.
-template <bool LDS_FACES, int GM, bool XSRC, bool COOP, bool HIST = false>
+// PHAS: the phasor tally (phasor.h, SMCRT_FLAG_PHASOR), done as HIST is: every line of it is under
+// `if constexpr (PHAS)`, except that the conditions of the far-field march and glance (far.h)
+// carry a constant `!PHAS`: a PHAS instantiation does not take them, since they cover many voxel
+// pieces in closed form and the tally needs each piece. They are bit-identical shortcuts, so the
+// ordinary path gives the same photon.
+template <bool LDS_FACES, int GM, bool XSRC, bool COOP, bool HIST = false, bool PHAS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCRT_WAVES_PER_EU_COOP : (XSRC ? SMCRT_WAVES_PER_EU_XSRC : SMCRT_WAVES_PER_EU)))) void transport_kernel(KParams K, const smcrt_sdf_node* __restrict__ nodes,
                                                         const ProgOp* __restrict__ prog,
                                                         const smcrt_detector* __restrict__ dets,
@@ -162,6 +168,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
   // HIST: this photon's path (vertex and record counts). An empty type otherwise: even a dead
   // PathLane changed the register allocation of the other instantiations.
   [[maybe_unused]] std::conditional_t<HIST, PathLane, NoPathLane> H;
+  // PHAS: this photon's phase and wavenumber; an empty type otherwise, for the same reason
+  [[maybe_unused]] std::conditional_t<PHAS, PhasLane, NoPhasLane> PH;
 
 #ifdef SMCRT_DIAG
   unsigned long long t_acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -256,7 +264,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
       // a glancing loop (ST_G0, inttau2.f90:226-237) that has run a while: tried at its 8th
       // iteration and every 64 after (a try whose certificate fails costs one extra EVAL)
       const uint64_t gcand =
-          K.fm_err > 0.0 ? __ballot(L.st == ST_G0 && L.pend && L.loopc >= SMCRT_FAR_MIN_LOOP &&
+          !PHAS && K.fm_err > 0.0 ? __ballot(L.st == ST_G0 && L.pend && L.loopc >= SMCRT_FAR_MIN_LOOP &&
                                     ((L.loopc - SMCRT_FAR_MIN_LOOP) & 63u) == 0)
                          : 0ull;
       // the full EVAL at q (every lane), and with `want` its far-field certificate (far.h): the
@@ -315,7 +323,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
         while (run) {
           const V3 q = v3(readlane_f64(L.pos.x, ow), readlane_f64(L.pos.y, ow), readlane_f64(L.pos.z, ow));
           // the far-field certificate of this EVAL, for a march that has run a while
-          const bool want = K.fm_err > 0.0 && __builtin_amdgcn_readlane((int)L.loopc, ow) >= SMCRT_FAR_MIN_LOOP;
+          const bool want = !PHAS && K.fm_err > 0.0 && __builtin_amdgcn_readlane((int)L.loopc, ow) >= SMCRT_FAR_MIN_LOOP;
           const EvalOut S = certified_eval(q, want);
           w_sdf += (uint32_t)K.n_top;  // ST_M1's ds array is counted (packet%cnts)
           if (lane_id == ow) {
@@ -352,7 +360,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
             bool dep = false;
             uint32_t vox = 0;
             double val = 0.0;
-            if (lane_id == ow) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight);
+            if constexpr (PHAS) {
+              DdaPiece pc;
+              if (lane_id == ow) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight, &pc);
+              phasor_piece(K, C, PH, pc, dep, vox, L.weight);
+            } else {
+              if (lane_id == ow) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight);
+            }
             w_dep += __popcll(__ballot(dep));
             if (binned) {
               if (K.bucket_tiles) emit_bucketed(K, C, WB, dep, vox, val, overflow, bstate);
@@ -363,7 +377,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
             }
           }
           run = __builtin_amdgcn_readlane((int)(L.st == ST_M1 && L.pend && !L.seg), ow) != 0;
-          if (run && fkind >= 0) {  // the far-field march from the certificate (far.h)
+          if (!PHAS && run && fkind >= 0) {  // the far-field march from the certificate (far.h)
             uint32_t n = 0, nsdf = 0;
             if (lane_id == ow) {
               double acc = 0.0;
@@ -392,7 +406,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
         const int ow = __builtin_ctzll(gcand);
         const V3 q = v3(readlane_f64(L.ssp.x, ow), readlane_f64(L.ssp.y, ow), readlane_f64(L.ssp.z, ow));
         certified_eval(q, true);
-        if (fkind >= 0) {
+        if (!PHAS && fkind >= 0) {
           uint32_t n = 0;
           if (lane_id == ow)
             n = fkind == SMCRT_SDF_BOX ? far_glance<SMCRT_SDF_BOX>(K, L, fnt, ftop, fm2)
@@ -621,7 +635,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
         bool dep = false;
         uint32_t vox = 0;
         double val = 0.0;
-        if (L.seg) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight);
+        if constexpr (PHAS) {
+          DdaPiece pc;
+          if (L.seg) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight, &pc);
+          phasor_piece(K, C, PH, pc, dep, vox, L.weight);
+        } else {
+          if (L.seg) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight);
+        }
         w_dep += __popcll(__ballot(dep));
         if (binned) {
           if (K.bucket_tiles) emit_bucketed(K, C, WB, dep, vox, val, overflow, bstate);
@@ -769,13 +789,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
           L.fault = false; L.layer = 0;
           LU(LU_STATUS) = 0; LU(LU_NSCATT) = 0; LU(LU_INTER) = 0; LU(LU_BOUNCES) = 0;
           L.xcell = L.ycell = L.zcell = 0;
-          emit<GM, XSRC>(K, C, L, XSRC ? LU(LU_ORIGIN) : 0u);
+          if constexpr (PHAS) emit<GM, XSRC>(K, C, L, XSRC ? LU(LU_ORIGIN) : 0u, &PH);
+          else emit<GM, XSRC>(K, C, L, XSRC ? LU(LU_ORIGIN) : 0u);
           if (!test_kernel) {
             int64_t tries = 0;
             while (cell_out(K, L)) {
               if (++tries > MAX_EMIT_TRIES) { L.fault = true; break; }
               LCTR(LC_RETRIES)++;
-              emit<GM, XSRC>(K, C, L, XSRC ? LU(LU_ORIGIN) : 0u);
+              if constexpr (PHAS) emit<GM, XSRC>(K, C, L, XSRC ? LU(LU_ORIGIN) : 0u, &PH);  // (phase and k again)
+              else emit<GM, XSRC>(K, C, L, XSRC ? LU(LU_ORIGIN) : 0u);
             }
             if (!L.fault && (K.flags & SMCRT_FLAG_RENDER_SOURCE)) add_cell(K, C->emission, L, 1.0);
           }

@@ -1,15 +1,16 @@
 // kinst.hip — one (LDS faces, grid mode) slice of the transport kernel instantiations.
-// Compiled fifteen times by build.py (-DKI_F=0/1 -DKI_G=0/1/2 -DKI_P=0/1, and -DKI_P=2 with
-// -DKI_F=0); see kernel_ptrs.h.
+// Compiled eighteen times by build.py (-DKI_F=0/1 -DKI_G=0/1/2 -DKI_P=0/1, and -DKI_P=2 and 3
+// with -DKI_F=0); see kernel_ptrs.h.
 // Part 0 holds transport_kernel and the XF ws_kernel, part 1 the plain ws_kernel (the lean path
 // of M1), which build.py compiles with its own scheduler flags (see UNITS there), part 2 the
 // HIST instantiations of transport_kernel (the photon path recorder, paths.h; faces in device
-// memory only), in units of their own so that they build beside the others.
+// memory only), in units of their own so that they build beside the others, part 3 likewise the
+// PHAS instantiations (the phasor tally, phasor.h). Nothing is instantiated for PHAS && HIST.
 #include "kernels.h"
 #include "kernel_ptrs.h"
 
 #if !defined(KI_F) || !defined(KI_G) || !defined(KI_P)
-#error "kinst.hip is compiled with -DKI_F=<0|1> -DKI_G=<0|1|2> -DKI_P=<0|1|2> (rsmcrt_amd/build.py)"
+#error "kinst.hip is compiled with -DKI_F=<0|1> -DKI_G=<0|1|2> -DKI_P=<0|1|2|3> (rsmcrt_amd/build.py)"
 #endif
 #define KI_NAME3(a, f, g) a##_##f##_##g
 #define KI_NAME2(a, f, g) KI_NAME3(a, f, g)
@@ -17,7 +18,18 @@
 
 namespace smcrt {
 
-#if KI_P == 2
+#if KI_P == 3
+#if KI_F != 0
+#error "the PHAS instantiations (KI_P=3) exist with KI_F=0 only"
+#endif
+const void* KI_NAME(kinst_transport_phas)(int xsrc, int coop) {
+  if (xsrc && coop) return (const void*)transport_kernel<false, KI_G, true, true, false, true>;
+  if (xsrc) return (const void*)transport_kernel<false, KI_G, true, false, false, true>;
+  if (coop) return (const void*)transport_kernel<false, KI_G, false, true, false, true>;
+  return (const void*)transport_kernel<false, KI_G, false, false, false, true>;
+}
+#define KI_DIAG_NAME KI_NAME(kinst_diagf)
+#elif KI_P == 2
 #if KI_F != 0
 #error "the HIST instantiations (KI_P=2) exist with KI_F=0 only"
 #endif

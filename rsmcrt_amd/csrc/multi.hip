@@ -452,6 +452,8 @@ static void discard_locked(smcrt_multi* m) {
 static int accumulate_locked(smcrt_multi* m, const smcrt_source* src, const smcrt_run_config* cfg) {
   if (cfg->flags & SMCRT_FLAG_TRACK_PATHS)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
+  if (cfg->flags & SMCRT_FLAG_PHASOR)
+    return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PHASOR: the phasor grid is tallied by smcrt_run only");
   if (cfg->flags & SMCRT_FLAG_RECORD_PHOTONS)
     return fail(SMCRT_ERR_INVALID_ARG, "photon records are not kept by the multi-GPU path (use smcrt_run)");
   const size_t n = m->devices.size();

@@ -163,6 +163,7 @@ inline size_t lean_lds(const ScenePlan& p) {
 inline uint32_t dep_words(const ScenePlan& p) { return p.bucketed ? 2 * p.n_tiles : 4 * p.hist_tiles; }
 // Dynamic LDS of the transport kernel: staged props + faces, detector start points, then the
 // deposit words, then the coop table.
+// (`hist`: also the phasor tally's instantiations, which keep their faces there too)
 inline size_t transport_lds(const ScenePlan& p, uint32_t dep_words, bool xsrc, bool hist = false) {
   const bool ctab = !p.ctab.empty() && p.coop_lanes > 0;  // the COOP instantiations stage it
   // (the general emitter with the COOP machinery and the path recorder keep their faces in
@@ -201,11 +202,11 @@ inline bool launch_binned(const ScenePlan& p, bool has_jmean, uint32_t flags) {
          !p.force_atomic;
 }
 // the lean path (ws_kernel, ws.h) when the scene and the run qualify: bucketed path-length
-// deposition, unit weights (no survival bias), a plain source, no path tracking (ws_kernel has
-// no recorder)
+// deposition, unit weights (no survival bias), a plain source, no path tracking and no phasor
+// tally (ws_kernel has neither)
 inline bool launch_lean(bool lean_ok, bool xsrc, uint32_t bucket_tiles, uint32_t flags) {
   return !xsrc && lean_ok && bucket_tiles && (flags & SMCRT_FLAG_PATHLENGTH) &&
-         !(flags & (SMCRT_FLAG_SURVIVAL_BIAS | SMCRT_FLAG_TRACK_PATHS));
+         !(flags & (SMCRT_FLAG_SURVIVAL_BIAS | SMCRT_FLAG_TRACK_PATHS | SMCRT_FLAG_PHASOR));
 }
 // ws_kernel's in-voxel segments (ws.h): on by default in the plain instantiation; the XF one
 // (xf: Fresnel interfaces or detectors), which measured slower with them, only when asked for

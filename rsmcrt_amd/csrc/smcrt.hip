@@ -179,6 +179,11 @@ struct smcrt_scene : ScenePlan {
   DevBuf<unsigned long long> d_path_ctl;
   uint64_t hist_lanes = 0;
   int grid_blocks_hist[2] = {0, 0};  // the HIST instantiations' grids (plain, XSRC)
+  // the phasor tally (smcrt_scene_set_phasor; phasor.h): the grid, 2 doubles per voxel
+  bool phasor_on = false;
+  smcrt_phasor_config phasor_cfg{};
+  DevBuf<double> d_phasor;
+  int grid_blocks_phas[2] = {0, 0};  // the PHAS instantiations' grids (plain, XSRC)
   std::mutex mu;
 };
 
@@ -208,11 +213,11 @@ static hipError_t harvest_times(smcrt_scene* s) {
 // and culling; it costs registers (scratch spills), so small scenes never pay for it. With the
 // general emitter (XSRC: other sources, batched origins, composites below the top level) that
 // is transport_kernel<.., true, true> (round 4; before, such scenes ran the serial EVAL).
-static const void* transport_fn(const smcrt_scene* s, bool xsrc, bool hist = false) {
+static const void* transport_fn(const smcrt_scene* s, bool xsrc, bool hist = false, bool phas = false) {
   // (the general emitter with the COOP machinery is instantiated with faces in device memory
   // only: three kernels instead of six, the library's build time, for the rare scenes that run
   // it; transport_lds follows)
-  return transport_kernel_ptr(s->lds_faces, s->grid_mode, xsrc, s->coop_lanes > 0, hist);
+  return transport_kernel_ptr(s->lds_faces, s->grid_mode, xsrc, s->coop_lanes > 0, hist, phas);
 }
 
 // ---- the watchdog (transport.h watchdog_expired): d_queue[Q_WATCHDOG] holds the first
@@ -620,9 +625,11 @@ static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xs
   const uint64_t blocks_needed = (waves_needed + 3) / 4;
   const uint64_t ws_needed = (Ch.n_photons + kinst_ws_photon_lanes() - 1) / kinst_ws_photon_lanes();
   const bool hist = (K.flags & SMCRT_FLAG_TRACK_PATHS) && s->path_on;  // (never lean: launch_lean)
+  const bool phas = (K.flags & SMCRT_FLAG_PHASOR) && s->phasor_on && !hist;  // (likewise; never with hist: smcrt_run)
   const int blocks = (int)std::min<uint64_t>(
       (uint64_t)(lean ? s->grid_blocks_ws
-                      : hist ? s->grid_blocks_hist[xsrc ? 1 : 0] : (xsrc ? s->grid_blocks_x : s->grid_blocks)),
+                      : hist ? s->grid_blocks_hist[xsrc ? 1 : 0]
+                             : phas ? s->grid_blocks_phas[xsrc ? 1 : 0] : (xsrc ? s->grid_blocks_x : s->grid_blocks)),
       std::max<uint64_t>(1, lean ? ws_needed : blocks_needed));
   const smcrt_sdf_node* a_nodes = K.nodes;
   const ProgOp* a_prog = K.prog;
@@ -636,8 +643,8 @@ static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xs
     const smcrt_detector* a_dets = K.dets;
     const int64_t* a_off = K.det_off;
     void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&a_dets, (void*)&a_off, (void*)&C};
-    HIPCHK(hipLaunchKernel(transport_fn(s, xsrc, hist), dim3(blocks), dim3(256), args,
-                           transport_lds(*s, dep_words(*s), xsrc, hist), stream));
+    HIPCHK(hipLaunchKernel(transport_fn(s, xsrc, hist, phas), dim3(blocks), dim3(256), args,
+                           transport_lds(*s, dep_words(*s), xsrc, hist || phas), stream));
   }
   HIPCHK(hipGetLastError());
   if (ev) HIPCHK(hipEventRecord(ev[1], stream));
@@ -824,6 +831,14 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.range_first = hist ? s->path_cfg.range_first : 0;
   Ch.range_count = hist ? s->path_cfg.range_count : 0;
   Ch.hist_max_vertices = hist ? (uint32_t)s->path_cfg.max_vertices : 0;
+  // the phasor tally: the wavenumber of photons that sample no wavelength of their own is the
+  // fixed one, or 2 pi / the constant spectrum's value (NULL spectrum: 500.0, smcrt.h)
+  const bool phas = (cfg->flags & SMCRT_FLAG_PHASOR) && s->phasor_on;
+  Ch.phasor = phas ? (double*)s->d_phasor : nullptr;
+  Ch.phasor_fixed = phas && s->phasor_cfg.fixed_k ? 1u : 0u;
+  Ch.phasor_k = !phas ? 0.0
+                : s->phasor_cfg.fixed_k ? s->phasor_cfg.wavenumber
+                                        : 6.283185307179586 / (src->spectrum ? src->spectrum->wavelength : 500.0);
 #ifdef SMCRT_DIAG
   Ch.done_time = nullptr;
   Ch.done_base = cfg->first_photon;
@@ -971,6 +986,8 @@ int smcrt_run_device(smcrt_scene* s, const smcrt_source* src, const smcrt_run_co
   if (!s || !src || !cfg || !dev) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
   if (cfg->flags & SMCRT_FLAG_TRACK_PATHS)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
+  if (cfg->flags & SMCRT_FLAG_PHASOR)
+    return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PHASOR: the phasor grid is tallied by smcrt_run only");
   std::lock_guard<std::mutex> g(s->mu);
   HIPCHK(hipSetDevice(s->device));
   return launch(s, src, cfg, *dev, (hipStream_t)stream);
@@ -1059,6 +1076,12 @@ int smcrt_run(smcrt_scene* s, const smcrt_source* src, const smcrt_run_config* c
   const bool track = (cfg->flags & SMCRT_FLAG_TRACK_PATHS) != 0;
   if (track && !s->path_on)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS needs smcrt_scene_set_path_tracking first");
+  if (cfg->flags & SMCRT_FLAG_PHASOR) {
+    if (!s->phasor_on) return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PHASOR needs smcrt_scene_set_phasor first");
+    if (track) return fail(SMCRT_ERR_UNSUPPORTED, "SMCRT_FLAG_PHASOR and SMCRT_FLAG_TRACK_PATHS do not combine");
+    if (!(cfg->flags & SMCRT_FLAG_PATHLENGTH))
+      return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PHASOR needs SMCRT_FLAG_PATHLENGTH (the tally lives in the voxel walk)");
+  }
   HIPCHK(hipSetDevice(s->device));
   if (track)  // a tracking run starts with an empty arena
     HIPCHK(hipMemsetAsync(s->d_path_ctl, 0, 3 * sizeof(unsigned long long), s->stream));
@@ -1072,6 +1095,8 @@ int smcrt_run_origins(smcrt_scene* s, const smcrt_source* src, const double* ori
   if (n_origins < 0) return fail(SMCRT_ERR_INVALID_ARG, "n_origins < 0");
   if (cfg->flags & SMCRT_FLAG_TRACK_PATHS)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
+  if (cfg->flags & SMCRT_FLAG_PHASOR)
+    return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PHASOR: the phasor grid is tallied by smcrt_run only");
   if (cfg->flags & SMCRT_FLAG_RECORD_PHOTONS) return fail(SMCRT_ERR_INVALID_ARG, "photon records are not kept for batched origins");
   if (n_origins > 0xFFFFFFFFll) return fail(SMCRT_ERR_INVALID_ARG, "more than 2^32 origins");
   if (n_origins == 0 || cfg->n_photons == 0) return SMCRT_OK;
@@ -1339,6 +1364,63 @@ int smcrt_scene_read_paths(smcrt_scene* s, smcrt_path* paths, double* vertices) 
     std::memcpy(vertices + 4 * off, arena.data() + slot * mv * 4, (size_t)hdr[slot].n_stored * 4 * sizeof(double));
     off += hdr[slot].n_stored;
   }
+  return SMCRT_OK;
+}
+
+// ---- the phasor tally (phasor.h) ----------------------------------------------------
+int smcrt_scene_set_phasor(smcrt_scene* s, const smcrt_phasor_config* cfg) {
+  g_last_error.clear();
+  if (cfg && cfg->fixed_k && !(cfg->wavenumber >= 0.0 && cfg->wavenumber <= 0x1.fffffffffffffp+1023))
+    return fail(SMCRT_ERR_INVALID_ARG, "phasor: a fixed wavenumber must be finite and >= 0");  // (before any device call)
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  std::lock_guard<std::mutex> g(s->mu);
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));  // (no launch of this scene may still use the grid)
+  s->phasor_on = false;
+  s->d_phasor.reset();
+  if (!cfg) return SMCRT_OK;
+  for (int x = 0; x < 2; ++x) {  // the PHAS instantiations' persistent grids
+    int per_cu = 0;
+    const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &per_cu, transport_fn(s, x == 1, false, true), 256, transport_lds(*s, dep_words(*s), x == 1, true));
+    if (oe != hipSuccess || per_cu < 1) per_cu = 1;
+    s->grid_blocks_phas[x] = s->n_cus * per_cu;
+  }
+  const size_t n2 = 2 * (size_t)s->grid.nx * (size_t)s->grid.ny * (size_t)s->grid.nz;
+  if (const int st = dalloc(s->d_phasor, n2)) {
+    (void)hipGetLastError();
+    s->d_phasor.reset();
+    return st;
+  }
+  HIPCHK(hipMemset(s->d_phasor, 0, n2 * sizeof(double)));
+  s->phasor_cfg = *cfg;
+  s->phasor_on = true;
+  return SMCRT_OK;
+}
+
+int smcrt_scene_read_phasor(smcrt_scene* s, double* out) {
+  g_last_error.clear();
+  if (!s || !out) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> g(s->mu);
+  if (!s->phasor_on) return fail(SMCRT_ERR_INVALID_ARG, "the phasor tally is not configured on this scene");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  const size_t n2 = 2 * (size_t)s->grid.nx * (size_t)s->grid.ny * (size_t)s->grid.nz;
+  std::vector<double> h(n2);
+  HIPCHK(hipMemcpy(h.data(), s->d_phasor, n2 * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n2; ++i) out[i] += h[i];
+  return SMCRT_OK;
+}
+
+int smcrt_scene_reset_phasor(smcrt_scene* s) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  std::lock_guard<std::mutex> g(s->mu);
+  if (!s->phasor_on) return fail(SMCRT_ERR_INVALID_ARG, "the phasor tally is not configured on this scene");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  const size_t n2 = 2 * (size_t)s->grid.nx * (size_t)s->grid.ny * (size_t)s->grid.nz;
+  HIPCHK(hipMemset(s->d_phasor, 0, n2 * sizeof(double)));
   return SMCRT_OK;
 }
 

@@ -20,6 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/smcrt.h"
 #include "detmath.h"
 #include "geometry.h"
@@ -100,6 +102,11 @@ struct KCold {
   uint64_t path_max;          // arena slots
   uint64_t range_first, range_count;  // the range trigger
   uint32_t hist_max_vertices;
+  // the phasor tally (SMCRT_FLAG_PHASOR; read by the PHAS instantiations of transport_kernel only,
+  // null / 0 otherwise; phasor.h). After the path fields, so that those stay where they were.
+  uint32_t phasor_fixed;      // != 0: every photon's wavenumber is phasor_k (smcrt_phasor_config::fixed_k)
+  double* phasor;             // [nx*ny*nz][2]: re, im interleaved, voxel order as jmean
+  double phasor_k;            // the fixed wavenumber, or 2 pi / the constant spectrum's wavelength
 };
 
 // watchdog sites (KCold::watchdog bits 0-7; smcrt.hip names them)
@@ -442,6 +449,20 @@ struct LaneShared {
   // (startPos of the detector segments, inttau2.f90:59,125-131, is in dynamic LDS and only
   // allocated when the scene has detectors)
 };
+// The phase state of a lane of a PHAS instantiation (phasor.h): the reference's packet%phase
+// and packet%fact. The other instantiations hold the empty type in its place (as NoPathLane,
+// paths.h: a dead local alone changed their register allocation).
+struct PhasLane {
+  double phase = 0.0;  // emitter phase + path length walked through the grid
+  double k = 0.0;      // wavenumber, 2 pi / wavelength
+};
+struct NoPhasLane {};
+// What a PHAS instantiation takes from one voxel crossing besides the deposit (dda_step_r).
+struct DdaPiece {
+  double dc = 0.0;    // the piece's length in fp64 (dcell after the d_sdf - d clamp)
+  bool wall = false;  // the piece ended on a voxel wall (ok && !last), the grid's outer walls included
+};
+struct NoDdaPiece {};
 #define LCTR(c) (sh->ctr[(c)][threadIdx.x])
 #define LU(f) (sh->u[(f)][threadIdx.x])
 
@@ -561,9 +582,15 @@ constexpr int MAX_RANG_TRIES = 1000;  // rang's rejection loop (random_mod.f90:1
 
 // pos/dir of one emission for every source kind (the cells are set by the caller)
 // `oidx`: the lane's origin in a batched point-source run (SrcPlan::origins).
-__device__ __forceinline__ void emit_ext(const KParams& K, const SrcPlan& P, Lane& L, uint32_t oidx) {
+// `ph` (PHAS instantiations): takes the emission's phase (dslit and aperture: the distance from
+// the sampled aperture point, photon.f90:755,823; 0 otherwise) and wavenumber 2 pi / the sampled
+// wavelength (photon%fact; slm has no wavelength to sample and keeps the reference's 500e-9,
+// photon.f90:202-204).
+template <class PH = NoPhasLane>
+__device__ __forceinline__ void emit_ext(const KParams& K, const SrcPlan& P, Lane& L, uint32_t oidx, PH* ph = nullptr) {
   const double TWOPI = 6.283185307179586;
   double wl, tmp;
+  if constexpr (!std::is_empty_v<PH>) ph->phase = 0.0;
   switch (P.kind) {
     case SMCRT_SRC_POINT: {  // photon.f90:311-359
       if (P.origins) {  // set_photon(voxel centre) before each run_MCRT, kernelsMod.f90:579-580
@@ -670,6 +697,7 @@ __device__ __forceinline__ void emit_ext(const KParams& K, const SrcPlan& P, Lan
                  P.origin[2]);
       L.dir = v3(P.dir[0], P.dir[1], P.dir[2]);
       L.layer = 1;
+      if constexpr (!std::is_empty_v<PH>) wl = 500.e-9;
       break;
     }
     default: {  // dslit :712-780, aperture :782-848
@@ -702,17 +730,29 @@ __device__ __forceinline__ void emit_ext(const KParams& K, const SrcPlan& P, Lan
       const double dx = x2 - x1, dy = y2 - y1, dz = z2 - z1;
       const double phase = sqrt(dx * dx + dy * dy + dz * dz);
       L.dir = v3(dx / phase, dy / phase, -fabs(dz) / phase);
+      if constexpr (!std::is_empty_v<PH>) ph->phase = phase;
       break;
     }
   }
+  if constexpr (!std::is_empty_v<PH>) ph->k = TWOPI / wl;
 }
 
 // emit: point photon.f90:311-359 / uniform :566-649 / pencil :652-710
-template <int GM, bool XSRC>
-__device__ __forceinline__ void emit(const KParams& K, const KCold* __restrict__ C, Lane& L, uint32_t oidx) {
+// `ph` (PHAS instantiations): the emission's phase and wavenumber; the three-source emitter
+// samples no spectrum, so its wavenumber is the launch's (KCold::phasor_k).
+template <int GM, bool XSRC, class PH = NoPhasLane>
+__device__ __forceinline__ void emit(const KParams& K, const KCold* __restrict__ C, Lane& L, uint32_t oidx,
+                                     PH* ph = nullptr) {
   const smcrt_source& s = C->src;
+  if constexpr (!std::is_empty_v<PH>) {
+    ph->phase = 0.0;
+    ph->k = C->phasor_k;
+  }
   if constexpr (XSRC) {
-    emit_ext(K, C->plan, L, oidx);
+    emit_ext(K, C->plan, L, oidx, ph);
+    if constexpr (!std::is_empty_v<PH>) {
+      if (C->phasor_fixed) ph->k = C->phasor_k;
+    }
   } else if (s.kind == SMCRT_SRC_POINT) {
     L.pos = v3(s.pos[0], s.pos[1], s.pos[2]);
     const double phi = L.rng.next(K.key0, K.key1) * 6.283185307179586;
@@ -813,23 +853,27 @@ __device__ __forceinline__ bool start_segment(const KParams& K, Lane& L, LaneSha
 // the photon's own Lane, or a walker's segment (lean.h); `dir` is the segment's direction.
 // (dda_step_r: the same crossing with the direction's refined reciprocals (ieee_rcp_f64 of
 // each component) supplied by the caller, e.g. kept by a walker for its whole segment.)
-template <int GM, class S>
+// `piece` (a DdaPiece*, the PHAS instantiations of transport_kernel): also hands out the piece's
+// fp64 length and whether it ended on a voxel wall. Every other caller leaves it out; the
+// parameter is then a null pointer to an empty type and nothing is computed for it.
+template <int GM, class S, class PC = NoDdaPiece>
 __device__ __forceinline__ void dda_step_r(const KParams& K, S& L, const V3 dir, const V3 rcp,
                                            const double* __restrict__ xf, const double* __restrict__ yf,
                                            const double* __restrict__ zf, bool& dep, uint32_t& dep_vox,
-                                           double& dep_val, double weight);
-template <int GM, class S>
+                                           double& dep_val, double weight, PC* piece = nullptr);
+template <int GM, class S, class PC = NoDdaPiece>
 __device__ __forceinline__ void dda_step(const KParams& K, S& L, const V3 dir, const double* __restrict__ xf,
                                          const double* __restrict__ yf, const double* __restrict__ zf,
-                                         bool& dep, uint32_t& dep_vox, double& dep_val, double weight) {
+                                         bool& dep, uint32_t& dep_vox, double& dep_val, double weight,
+                                         PC* piece = nullptr) {
   const V3 rcp = v3(ieee_rcp_f64(dir.x), ieee_rcp_f64(dir.y), ieee_rcp_f64(dir.z));
-  dda_step_r<GM>(K, L, dir, rcp, xf, yf, zf, dep, dep_vox, dep_val, weight);
+  dda_step_r<GM>(K, L, dir, rcp, xf, yf, zf, dep, dep_vox, dep_val, weight, piece);
 }
-template <int GM, class S>
+template <int GM, class S, class PC>
 __device__ __forceinline__ void dda_step_r(const KParams& K, S& L, const V3 dir, const V3 rcp3,
                                            const double* __restrict__ xf, const double* __restrict__ yf,
                                            const double* __restrict__ zf, bool& dep, uint32_t& dep_vox,
-                                           double& dep_val, double weight) {
+                                           double& dep_val, double weight, PC* piece) {
 #ifdef SMCRT_ASM_MARKERS
   asm volatile("; @@DDA_BEGIN");
 #endif
@@ -895,6 +939,10 @@ __device__ __forceinline__ void dda_step_r(const KParams& K, S& L, const V3 dir,
   dep = ok;
   dep_vox = lin(K, L.xcell, L.ycell, L.zcell);
   dep_val = (double)(float)dc * weight;
+  if constexpr (!std::is_empty_v<PC>) {
+    piece->dc = dc;
+    piece->wall = ok && !last;
+  }
   // update_pos (:524-584): .false. (last step) advances all three coordinates by dc;
   // .true. snaps the first axis with ldir set to its wall +- delta (unchanged if its
   // direction is 0) and advances the other two.

@@ -101,6 +101,9 @@ def load_library(path: str = LIB_PATH):
         L.smcrt_scene_set_path_tracking.argtypes = [C.c_void_p, C.POINTER(abi.PathConfig)]
         L.smcrt_scene_path_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4
         L.smcrt_scene_read_paths.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.smcrt_scene_set_phasor.argtypes = [C.c_void_p, C.POINTER(abi.PhasorConfig)]
+        L.smcrt_scene_read_phasor.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.smcrt_scene_reset_phasor.argtypes = [C.c_void_p]
         L.smcrt_displacement_compile.argtypes = [C.c_char_p, C.POINTER(abi.SdfNode)]
         L.smcrt_displacement_eval.argtypes = [C.POINTER(abi.SdfNode), C.POINTER(C.c_double), C.c_int64,
                                               C.POINTER(C.c_double)]
@@ -310,6 +313,33 @@ class Engine:
             _check(L.smcrt_scene_read_paths(self._h, hdr.ctypes.data_as(C.c_void_p),
                                             vtx.ctypes.data_as(C.POINTER(C.c_double))))
         return hdr, vtx, counts
+
+    def set_phasor(self, wavenumber="sampled"):
+        """Configure the phasor tally (smcrt_scene_set_phasor): runs made with abi.FLAG_PHASOR then
+        add weight * exp(i k phase) to the voxel a photon leaves at every voxel wall it crosses.
+        `set_phasor()` takes k = 2 pi / the wavelength each emission samples, `set_phasor(k)` a
+        fixed wavenumber (finite, >= 0) for every photon, `set_phasor(None)` turns the tally off
+        and frees the grid."""
+        L = load_library()
+        if wavenumber is None:
+            _check(L.smcrt_scene_set_phasor(self._h, None))
+            return
+        cfg = abi.PhasorConfig()
+        if not (isinstance(wavenumber, str) and wavenumber == "sampled"):
+            cfg.fixed_k, cfg.wavenumber = 1, float(wavenumber)
+        _check(L.smcrt_scene_set_phasor(self._h, C.byref(cfg)))
+
+    def phasor(self) -> np.ndarray:
+        """The scene's phasor grid (smcrt_scene_read_phasor) as a complex128 array of shape
+        (nz, ny, nx), ordered like Result.jmean; it accumulates over runs until reset_phasor."""
+        g = self.grid
+        out = np.zeros((g.nz, g.ny, g.nx), dtype=np.complex128)
+        _check(load_library().smcrt_scene_read_phasor(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def reset_phasor(self):
+        """Zero the scene's phasor grid (smcrt_scene_reset_phasor)."""
+        _check(load_library().smcrt_scene_reset_phasor(self._h))
 
     def invoxel_segments(self) -> int:
         """Deposit segments of the scene's finished launches that the lean path's photon waves

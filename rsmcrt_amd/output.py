@@ -86,6 +86,21 @@ def write_paths(filename, headers, vertices) -> None:
                                     v.ctypes.data_as(C.POINTER(C.c_double))))
 
 
+def write_phasor(fileplace, outfile, phasor, metadata: str | None = None, overwrite: bool = True) -> str:
+    """abs(phasor)**2 as fp32 to <fileplace>/phasor/<outfile> through write_data: the line
+    `finalise` carries commented out (kernelsMod.f90:2395). `phasor` is Engine.phasor()'s
+    complex array of shape (nz, ny, nx); the phasor/ directory is created if missing (setup.f90
+    directory()). Returns the file name actually written."""
+    import os
+    p = np.asarray(phasor)
+    if not np.iscomplexobj(p) or p.ndim != 3:
+        raise ValueError("phasor must be a complex array of shape (nz, ny, nx)")
+    d = os.path.join(str(fileplace), "phasor")
+    os.makedirs(d, exist_ok=True)
+    return write_data(os.path.join(d, str(outfile)), (np.abs(p) ** 2).astype(np.float32), metadata,
+                      overwrite=overwrite)
+
+
 def normalise_fluence(jmean, grid: abi.Grid, nphotons: int) -> np.ndarray:
     """normalise_fluence, writer.f90:25-52, on an fp32 copy (the reference's array kind)."""
     a = np.array(jmean, dtype=np.float32, copy=True, order="C")
