@@ -329,6 +329,33 @@ int smcrt_scene_create(const smcrt_sdf_node* nodes, int32_t n_nodes,
                        int32_t device, smcrt_scene** out);
 void smcrt_scene_destroy(smcrt_scene* scene);
 
+/* ---- voxel media -----------------------------------------------------------------------------
+ * A second kind of scene: the grid, one label per voxel and a table of media; no SDF. A photon
+ * walks the grid voxel by voxel; where the refractive index changes between two voxels it meets
+ * an interface whose normal is that of the voxel wall it crossed (axis-aligned: a curved surface
+ * between media of different index is a staircase). The world ends at the grid.
+ *   labels[nx*ny*nz]: x fastest (the order of jmean), 0-based indices into media[n_media],
+ *   1 <= n_media <= 256. kappa and albedo of a medium follow smcrt_scene_create's rule for a
+ *   layer (albedo = 1 when mua < 1e-9); kappa == 0 is a void. A photon's `layer` (photon records,
+ *   detectors) is its medium index + 1.
+ * Every argument is validated before any device call: a failed validation gives
+ * SMCRT_ERR_INVALID_ARG with a message (a label >= n_media names the first offending voxel);
+ * valid arguments without a GPU give SMCRT_ERR_NO_DEVICE. The result is an ordinary smcrt_scene:
+ * smcrt_run, smcrt_run_device (same launch path; both refuse SMCRT_FLAG_TEST_KERNEL, _END_EARLY,
+ * _TRACK_PATHS and _PHASOR with SMCRT_ERR_UNSUPPORTED), smcrt_scene_info (n_top = n_media),
+ * smcrt_scene_det_bins, smcrt_scene_check, smcrt_scene_fence, smcrt_scene_set_timing,
+ * smcrt_scene_kernel_times, smcrt_scene_set_optprops / _get_optprops (index = medium; layer =
+ * index + 1), smcrt_scene_classify (label + 1 and kappa of the voxel the point is in, 0 outside
+ * the grid) and smcrt_scene_destroy work on it. Every other entry point that takes a scene
+ * (smcrt_run_origins, smcrt_escape_run, smcrt_inverse_run, smcrt_scene_set_spectral, path
+ * tracking, the phasor, smcrt_scene_invoxel_segments, smcrt_reduce_device_tallies) answers
+ * SMCRT_ERR_UNSUPPORTED with a message naming voxel scenes. */
+typedef struct smcrt_medium { double mus, mua, hgg, n; } smcrt_medium;
+
+int smcrt_voxel_scene_create(const uint8_t* labels, const smcrt_medium* media, int32_t n_media,
+                             const smcrt_grid* grid, const smcrt_detector* dets, int32_t n_dets,
+                             int32_t device, smcrt_scene** out);
+
 /* The scene's fluence grid, number of top-level SDFs and of detectors (any may be NULL). */
 int smcrt_scene_info(const smcrt_scene* scene, smcrt_grid* grid, int32_t* n_top, int32_t* n_dets);
 
@@ -607,6 +634,17 @@ typedef struct smcrt_kernel_times {
 
 int smcrt_scene_set_timing(smcrt_scene* scene, int32_t enable);
 int smcrt_scene_kernel_times(smcrt_scene* scene, smcrt_kernel_times* out);
+
+/* How the scene's plan files the jmean deposits of a run with SMCRT_FLAG_PATHLENGTH, unit weights
+ * (no SMCRT_FLAG_SURVIVAL_BIAS) and a jmean tally; any other run adds with fp64 atomics. Decided
+ * at scene creation from the grid and SMCRT_DEPOSIT; works on SDF and voxel
+ * scenes, makes no device call. */
+enum {
+  SMCRT_DEPOSIT_ATOMIC = 0,  /* fp64 atomics into jmean */
+  SMCRT_DEPOSIT_SORTED = 1,  /* records sorted by tile, then summed */
+  SMCRT_DEPOSIT_BUCKETS = 2  /* records filed into per-tile buckets, then summed */
+};
+int smcrt_scene_deposit_regime(const smcrt_scene* scene, int32_t* regime);
 
 /* The deposit segments (update_grids calls, SMCRT_CTR_GRID_UPDATES) of this scene's finished
  * launches that the lean path's photon waves deposited themselves because the segment provably

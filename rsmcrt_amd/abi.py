@@ -63,6 +63,10 @@ FLAG_OVERLAP = 1 << 7
 FLAG_TRACK_PATHS = 1 << 8  # smcrt_run only: record photon paths (Engine.set_path_tracking)
 FLAG_PHASOR = 1 << 9  # smcrt_run only: accumulate the complex phasor grid (Engine.set_phasor)
 
+# smcrt_scene_deposit_regime
+DEPOSIT_ATOMIC, DEPOSIT_SORTED, DEPOSIT_BUCKETS = 0, 1, 2
+DEPOSIT_REGIMES = {DEPOSIT_ATOMIC: "atomic", DEPOSIT_SORTED: "sorted", DEPOSIT_BUCKETS: "buckets"}
+
 # smcrt_detector.reserved, bit 0: the detector files the photon's path at every hit it scores
 DET_TRACK_HISTORY = 1
 
@@ -107,6 +111,11 @@ class OptProps(C.Structure):
     _fields_ = [("mus", C.c_double), ("mua", C.c_double), ("hgg", C.c_double), ("g2", C.c_double),
                 ("n", C.c_double), ("kappa", C.c_double), ("albedo", C.c_double), ("wavelength", C.c_double),
                 ("node_flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Medium(C.Structure):
+    """smcrt_medium: one entry of a voxel scene's table of media."""
+    _fields_ = [("mus", C.c_double), ("mua", C.c_double), ("hgg", C.c_double), ("n", C.c_double)]
 
 
 class Grid(C.Structure):
@@ -270,4 +279,5 @@ EXPORTED_SYMBOLS = [
     "smcrt_job_history_filename",
     "smcrt_scene_set_phasor", "smcrt_scene_read_phasor", "smcrt_scene_reset_phasor",
     "smcrt_displacement_compile", "smcrt_displacement_eval", "smcrt_displacement_describe",
+    "smcrt_voxel_scene_create", "smcrt_scene_deposit_regime",
 ]

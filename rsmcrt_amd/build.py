@@ -32,7 +32,9 @@ UNITS = [(src, ()) for src in SOURCES] + [
     # part 2: transport_kernel's photon path recorder (HIST, faces in device memory only)
     (KINST, ("-DKI_F=0", f"-DKI_G={g}", "-DKI_P=2")) for g in (0, 1, 2)] + [
     # part 3: transport_kernel's phasor tally (PHAS, faces in device memory only)
-    (KINST, ("-DKI_F=0", f"-DKI_G={g}", "-DKI_P=3")) for g in (0, 1, 2)]
+    (KINST, ("-DKI_F=0", f"-DKI_G={g}", "-DKI_P=3")) for g in (0, 1, 2)] + [
+    # part 4: voxel_kernel (voxel.h: label volumes; its faces are always staged in LDS)
+    (KINST, ("-DKI_F=0", f"-DKI_G={g}", "-DKI_P=4")) for g in (0, 1, 2)]
 DEPS = SOURCES + [KINST] + sorted(glob.glob(os.path.join(PKG, "csrc", "*.h"))) + [os.path.join(ROOT, "include", "smcrt.h")]
 ARCH = os.environ.get("SMCRT_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=off: no fused multiply-add, so fp64 trajectories are bit-identical to the

@@ -3,7 +3,8 @@
 // build.py compiles kinst.hip once per (LDS faces F, grid mode G, part P) with -DKI_F=F -DKI_G=G
 // -DKI_P=P (part 1: the plain ws_kernel, with its own scheduler flags; part 2, F = 0 only:
 // transport_kernel's HIST instantiations, the photon path recorder of paths.h; part 3, F = 0
-// only: its PHAS instantiations, the phasor tally of phasor.h), so
+// only: its PHAS instantiations, the phasor tally of phasor.h; part 4, F = 0 only: voxel_kernel,
+// the label-volume transport of voxel.h), so
 // the instantiations of transport_kernel and ws_kernel (kernels.h, ws.h) build in parallel
 // instead of in one translation unit. Each object exports these getters; hipLaunchKernel and
 // the occupancy queries take the host stubs they return.
@@ -44,6 +45,13 @@ SMCRT_KINST_PHAS_DECL(0)
 SMCRT_KINST_PHAS_DECL(1)
 SMCRT_KINST_PHAS_DECL(2)
 #undef SMCRT_KINST_PHAS_DECL
+#define SMCRT_KINST_VOXEL_DECL(G)              \
+  const void* kinst_voxel_0_##G(int xsrc);     \
+  void kinst_diagv_0_##G(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6);
+SMCRT_KINST_VOXEL_DECL(0)
+SMCRT_KINST_VOXEL_DECL(1)
+SMCRT_KINST_VOXEL_DECL(2)
+#undef SMCRT_KINST_VOXEL_DECL
 
 // transport_kernel<lds_faces, gm, xsrc, coop, hist, phas>; the general emitter with the COOP
 // machinery (xsrc && coop), the path recorder (hist, paths.h) and the phasor tally (phas,
@@ -65,6 +73,11 @@ inline const void* transport_kernel_ptr(bool lds_faces, int gm, bool xsrc, bool 
     case 4: return kinst_transport_1_1(x, c);
     default: return kinst_transport_1_2(x, c);
   }
+}
+// voxel_kernel<gm, xsrc> (voxel.h)
+inline const void* voxel_kernel_ptr(int gm, bool xsrc) {
+  const int x = xsrc ? 1 : 0;
+  return gm == 0 ? kinst_voxel_0_0(x) : gm == 1 ? kinst_voxel_0_1(x) : kinst_voxel_0_2(x);
 }
 // ws_kernel<lds_faces, gm, xf, slots, iv> (xf: the Fresnel/detector program points; slots 2 or 3;
 // iv: the in-voxel segments' code, always in the plain instantiation, ws.h)
@@ -90,6 +103,7 @@ inline void kinst_diag_gather(unsigned long long* d72, unsigned long long* t9, u
   kinst_diagp_1_0(d72, t9, c6); kinst_diagp_1_1(d72, t9, c6); kinst_diagp_1_2(d72, t9, c6);
   kinst_diagh_0_0(d72, t9, c6); kinst_diagh_0_1(d72, t9, c6); kinst_diagh_0_2(d72, t9, c6);
   kinst_diagf_0_0(d72, t9, c6); kinst_diagf_0_1(d72, t9, c6); kinst_diagf_0_2(d72, t9, c6);
+  kinst_diagv_0_0(d72, t9, c6); kinst_diagv_0_1(d72, t9, c6); kinst_diagv_0_2(d72, t9, c6);
 }
 
 }  // namespace smcrt

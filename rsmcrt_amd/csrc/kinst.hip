@@ -1,16 +1,20 @@
 // kinst.hip — one (LDS faces, grid mode) slice of the transport kernel instantiations.
-// Compiled eighteen times by build.py (-DKI_F=0/1 -DKI_G=0/1/2 -DKI_P=0/1, and -DKI_P=2 and 3
+// Compiled twenty-one times by build.py (-DKI_F=0/1 -DKI_G=0/1/2 -DKI_P=0/1, and -DKI_P=2, 3 and 4
 // with -DKI_F=0); see kernel_ptrs.h.
 // Part 0 holds transport_kernel and the XF ws_kernel, part 1 the plain ws_kernel (the lean path
 // of M1), which build.py compiles with its own scheduler flags (see UNITS there), part 2 the
 // HIST instantiations of transport_kernel (the photon path recorder, paths.h; faces in device
 // memory only), in units of their own so that they build beside the others, part 3 likewise the
 // PHAS instantiations (the phasor tally, phasor.h). Nothing is instantiated for PHAS && HIST.
+// Part 4 holds voxel_kernel (voxel.h: label volumes, no SDF), plain and general emitter.
 #include "kernels.h"
 #include "kernel_ptrs.h"
+#if defined(KI_P) && KI_P == 4
+#include "voxel.h"
+#endif
 
 #if !defined(KI_F) || !defined(KI_G) || !defined(KI_P)
-#error "kinst.hip is compiled with -DKI_F=<0|1> -DKI_G=<0|1|2> -DKI_P=<0|1|2|3> (rsmcrt_amd/build.py)"
+#error "kinst.hip is compiled with -DKI_F=<0|1> -DKI_G=<0|1|2> -DKI_P=<0|1|2|3|4> (rsmcrt_amd/build.py)"
 #endif
 #define KI_NAME3(a, f, g) a##_##f##_##g
 #define KI_NAME2(a, f, g) KI_NAME3(a, f, g)
@@ -18,7 +22,15 @@
 
 namespace smcrt {
 
-#if KI_P == 3
+#if KI_P == 4
+#if KI_F != 0
+#error "voxel_kernel (KI_P=4) is compiled with KI_F=0 only (its faces are always staged in LDS)"
+#endif
+const void* KI_NAME(kinst_voxel)(int xsrc) {
+  return xsrc ? (const void*)voxel_kernel<KI_G, true> : (const void*)voxel_kernel<KI_G, false>;
+}
+#define KI_DIAG_NAME KI_NAME(kinst_diagv)
+#elif KI_P == 3
 #if KI_F != 0
 #error "the PHAS instantiations (KI_P=3) exist with KI_F=0 only"
 #endif

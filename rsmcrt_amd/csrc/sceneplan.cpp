@@ -237,6 +237,58 @@ void plan_far_march(const smcrt_sdf_node* nodes, const int32_t* top, int32_t n_t
   }
 }
 
+// detector data offsets (a camera owns nbins^2 doubles)
+void plan_detectors(const smcrt_detector* dets, int32_t n_dets, ScenePlan& p) {
+  p.h_dets.assign(dets, dets + n_dets);
+  p.h_det_off.assign((size_t)n_dets + 1, 0);
+  for (int32_t i = 0; i < n_dets; ++i) {
+    const int64_t nb = dets[i].nbins;
+    p.h_det_off[i + 1] = p.h_det_off[i] + (dets[i].kind == SMCRT_DET_CAMERA ? nb * nb : nb);
+  }
+  p.det_total = p.h_det_off[n_dets];
+}
+
+// voxel faces, grid.f90:147-157: (i-1)*2*max/n; zface has nz+2 entries
+void plan_faces(const smcrt_grid* grid, ScenePlan& p) {
+  for (int32_t i = 0; i < grid->nx + 1; ++i) p.faces.push_back((double)i * 2.0 * grid->xmax / (double)grid->nx);
+  for (int32_t i = 0; i < grid->ny + 1; ++i) p.faces.push_back((double)i * 2.0 * grid->ymax / (double)grid->ny);
+  for (int32_t i = 0; i < grid->nz + 2; ++i) p.faces.push_back((double)i * 2.0 * grid->zmax / (double)grid->nz);
+}
+
+// inv2, fe and the kernels' grid mode
+void plan_grid_mode(const smcrt_grid* grid, ScenePlan& p) {
+  const double maxes[3] = {grid->xmax, grid->ymax, grid->zmax};
+  // n*p/(2*max) may be computed as n*p*inv exactly when 2*max is a power of two
+  for (int a = 0; a < 3; ++a) {
+    int ex = 0;
+    const double m = std::frexp(2.0 * maxes[a], &ex);
+    p.inv2[a] = (m == 0.5 && std::isfinite(1.0 / (2.0 * maxes[a]))) ? 1.0 / (2.0 * maxes[a]) : 0.0;
+  }
+  const bool p2 = p.inv2[0] != 0.0 && p.inv2[1] != 0.0 && p.inv2[2] != 0.0;
+  const int32_t ns[3] = {grid->nx, grid->ny, grid->nz};
+  bool f2 = p2;
+  for (int a = 0; a < 3; ++a) {
+    if ((ns[a] & (ns[a] - 1)) != 0) { f2 = false; continue; }
+    int e2m = 0, en = 0;  // 2*max = 2^(e2m-1), n = 2^(en-1)
+    (void)std::frexp(2.0 * maxes[a], &e2m);
+    (void)std::frexp((double)ns[a], &en);
+    p.fe[a] = e2m - en;  // face k = k * 2*max/n = k * 2^fe
+  }
+  p.grid_mode = f2 ? 2 : (p2 ? 1 : 0);
+}
+
+// binned deposition (deposit.h); SMCRT_DEPOSIT=sorted (or a disabled fused histogram) keeps the sorted record path
+void plan_deposit(const smcrt_grid* grid, const Knobs& knobs, ScenePlan& p) {
+  const uint64_t nv = (uint64_t)grid->nx * grid->ny * grid->nz;
+  const uint64_t tiles = (nv + TILE_VOXELS - 1) / TILE_VOXELS;
+  p.n_tiles = (tiles <= MAX_TILES && nv < 0xFFFFFFFFull) ? (uint32_t)tiles : 0;
+  p.force_atomic = knobs.deposit_atomic;
+  p.pool_cap_chunks = knobs.pool_cap_chunks;
+  const bool sorted = knobs.deposit_sorted || !knobs.fused_hist;
+  p.bucketed = !sorted && p.n_tiles > 0 && p.n_tiles <= MAX_DIRECT_TILES;
+  p.hist_tiles = (!p.bucketed && knobs.fused_hist && p.n_tiles > 0 && p.n_tiles <= MAX_FUSED_HIST_TILES) ? p.n_tiles : 0;
+}
+
 }  // namespace
 
 int plan_scene(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top, int32_t n_top, const smcrt_grid* grid,
@@ -250,17 +302,8 @@ int plan_scene(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top,
   p.h_nodes.assign(nodes, nodes + n_nodes);
   p.h_top.assign(top, top + n_top);
   for (int32_t i = 0; i < n_top; ++i) p.h_props.push_back(make_props(nodes[top[i]]));
-  p.h_dets.assign(dets, dets + n_dets);
-  p.h_det_off.assign((size_t)n_dets + 1, 0);
-  for (int32_t i = 0; i < n_dets; ++i) {
-    const int64_t nb = dets[i].nbins;
-    p.h_det_off[i + 1] = p.h_det_off[i] + (dets[i].kind == SMCRT_DET_CAMERA ? nb * nb : nb);
-  }
-  p.det_total = p.h_det_off[n_dets];
-  // voxel faces, grid.f90:147-157: (i-1)*2*max/n; zface has nz+2 entries
-  for (int32_t i = 0; i < grid->nx + 1; ++i) p.faces.push_back((double)i * 2.0 * grid->xmax / (double)grid->nx);
-  for (int32_t i = 0; i < grid->ny + 1; ++i) p.faces.push_back((double)i * 2.0 * grid->ymax / (double)grid->ny);
-  for (int32_t i = 0; i < grid->nz + 2; ++i) p.faces.push_back((double)i * 2.0 * grid->zmax / (double)grid->nz);
+  plan_detectors(dets, n_dets, p);
+  plan_faces(grid, p);
   flatten(nodes, top, n_top, p);
   // A sparse wave evaluates its lanes' SDF arrays one lane at a time across the wave when
   // that is cheaper than the serial per-lane chain over all n_top tops (transport.h).
@@ -283,35 +326,8 @@ int plan_scene(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top,
   // exact culling of the SDF array for many-top scenes (cull.h)
   if (p.coop_lanes > 0 && knobs.cull) p.cull = build_cull(nodes, n_nodes, top, n_top, maxes, knobs.cull_grid);
   if (!p.ctab.empty() || p.cull.enabled) plan_far_march(nodes, top, n_top, grid, knobs.far_march, p);
-  // n*p/(2*max) may be computed as n*p*inv exactly when 2*max is a power of two
-  for (int a = 0; a < 3; ++a) {
-    int ex = 0;
-    const double m = std::frexp(2.0 * maxes[a], &ex);
-    p.inv2[a] = (m == 0.5 && std::isfinite(1.0 / (2.0 * maxes[a]))) ? 1.0 / (2.0 * maxes[a]) : 0.0;
-  }
-  {
-    const bool p2 = p.inv2[0] != 0.0 && p.inv2[1] != 0.0 && p.inv2[2] != 0.0;
-    const int32_t ns[3] = {grid->nx, grid->ny, grid->nz};
-    bool f2 = p2;
-    for (int a = 0; a < 3; ++a) {
-      if ((ns[a] & (ns[a] - 1)) != 0) { f2 = false; continue; }
-      int e2m = 0, en = 0;  // 2*max = 2^(e2m-1), n = 2^(en-1)
-      (void)std::frexp(2.0 * maxes[a], &e2m);
-      (void)std::frexp((double)ns[a], &en);
-      p.fe[a] = e2m - en;  // face k = k * 2*max/n = k * 2^fe
-    }
-    p.grid_mode = f2 ? 2 : (p2 ? 1 : 0);
-  }
-  {  // binned deposition (deposit.h); SMCRT_DEPOSIT=sorted (or a disabled fused histogram) keeps the sorted record path
-    const uint64_t nv = (uint64_t)grid->nx * grid->ny * grid->nz;
-    const uint64_t tiles = (nv + TILE_VOXELS - 1) / TILE_VOXELS;
-    p.n_tiles = (tiles <= MAX_TILES && nv < 0xFFFFFFFFull) ? (uint32_t)tiles : 0;
-    p.force_atomic = knobs.deposit_atomic;
-    p.pool_cap_chunks = knobs.pool_cap_chunks;
-    const bool sorted = knobs.deposit_sorted || !knobs.fused_hist;
-    p.bucketed = !sorted && p.n_tiles > 0 && p.n_tiles <= MAX_DIRECT_TILES;
-    p.hist_tiles = (!p.bucketed && knobs.fused_hist && p.n_tiles > 0 && p.n_tiles <= MAX_FUSED_HIST_TILES) ? p.n_tiles : 0;
-  }
+  plan_grid_mode(grid, p);
+  plan_deposit(grid, knobs, p);
   p.face_bytes = p.faces.size() * sizeof(double) + sizeof(TopProps) * (size_t)n_top;
   p.lds_faces = p.face_bytes <= MAX_FACE_BYTES;
   for (int32_t i = 1; i < n_top; ++i) p.fresnel = p.fresnel || p.h_props[i].n != p.h_props[0].n;
@@ -335,6 +351,76 @@ int plan_scene(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top,
   p.cull_log = knobs.cull_log;
   p.verbose = knobs.verbose;
   return SMCRT_OK;
+}
+
+int plan_voxel_scene(const uint8_t* labels, const smcrt_medium* media, int32_t n_media, const smcrt_grid* grid,
+                     const smcrt_detector* dets, int32_t n_dets, const Knobs& knobs, ScenePlan* out) {
+  if (!labels || !media || !grid || n_dets < 0 || (n_dets > 0 && !dets))
+    return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: NULL argument");
+  if (n_media < 1 || n_media > 256)
+    return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: n_media = " + std::to_string(n_media) + " is outside 1 .. 256");
+  if (grid->nx < 1 || grid->ny < 1 || grid->nz < 1 || !(grid->xmax > 0) || !(grid->ymax > 0) || !(grid->zmax > 0) ||
+      !std::isfinite(grid->xmax) || !std::isfinite(grid->ymax) || !std::isfinite(grid->zmax))
+    return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: grid dimensions must be positive and finite");
+  const uint64_t nv = (uint64_t)grid->nx * (uint64_t)grid->ny * (uint64_t)grid->nz;
+  if (nv >= (1ull << 32)) return fail(SMCRT_ERR_UNSUPPORTED, "grids of 2^32 or more voxels are not supported");
+  for (int32_t i = 0; i < n_media; ++i) {
+    const smcrt_medium& m = media[i];
+    if (!(m.mus >= 0.0) || !(m.mua >= 0.0) || !std::isfinite(m.mus) || !std::isfinite(m.mua))
+      return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: medium " + std::to_string(i) + ": mus and mua must be finite and >= 0");
+    if (!(std::fabs(m.hgg) <= 1.0))
+      return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: medium " + std::to_string(i) + ": |hgg| must be <= 1");
+    if (!(m.n > 0.0) || !std::isfinite(m.n))
+      return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: medium " + std::to_string(i) + ": n must be finite and > 0");
+  }
+  for (uint64_t v = 0; v < nv; ++v)
+    if (labels[v] >= n_media) {
+      const uint64_t i = v % (uint64_t)grid->nx, j = (v / (uint64_t)grid->nx) % (uint64_t)grid->ny,
+                     k = v / ((uint64_t)grid->nx * (uint64_t)grid->ny);
+      return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: label " + std::to_string((int)labels[v]) + " of voxel (" +
+                                             std::to_string(i) + ", " + std::to_string(j) + ", " + std::to_string(k) +
+                                             ") (0-based, linear index " + std::to_string(v) + ") is not below n_media = " +
+                                             std::to_string(n_media));
+    }
+  for (int32_t i = 0; i < n_dets; ++i)
+    if (dets[i].kind < SMCRT_DET_CIRCLE || dets[i].kind > SMCRT_DET_FIBRE || dets[i].nbins < 1)
+      return fail(SMCRT_ERR_INVALID_ARG, "bad detector " + std::to_string(i));
+  ScenePlan& p = *out;
+  p.voxel = true;
+  p.n_nodes = p.n_top = n_media;
+  p.n_dets = n_dets;
+  p.grid = *grid;
+  p.labels.assign(labels, labels + nv);
+  for (int32_t i = 0; i < n_media; ++i) {  // a placeholder node per medium carries its mus, mua, hgg, n
+    smcrt_sdf_node nd;
+    std::memset(&nd, 0, sizeof nd);
+    nd.layer = i + 1;
+    nd.mus = media[i].mus; nd.mua = media[i].mua; nd.hgg = media[i].hgg; nd.n = media[i].n;
+    p.h_nodes.push_back(nd);
+    p.h_top.push_back(i);
+    p.h_props.push_back(make_props(nd));
+  }
+  plan_detectors(dets, n_dets, p);
+  plan_faces(grid, p);
+  plan_grid_mode(grid, p);
+  plan_deposit(grid, knobs, p);
+  // voxel_kernel stages the media and the faces in LDS whatever their size
+  p.face_bytes = p.faces.size() * sizeof(double) + sizeof(TopProps) * (size_t)n_media;
+  p.lds_faces = true;
+  if (p.face_bytes > MAX_FACE_BYTES)
+    return fail(SMCRT_ERR_UNSUPPORTED, "voxel scene: nx + ny + nz is too large for the faces to be staged in LDS");
+  for (int32_t i = 1; i < n_media; ++i) p.fresnel = p.fresnel || p.h_props[i].n != p.h_props[0].n;
+  p.lean_mode = 0;
+  p.lean_candidate = false;  // ws_kernel has no label walk
+  p.fold_prio = knobs.fold_prio;
+  p.verbose = knobs.verbose;
+  return SMCRT_OK;
+}
+
+int32_t host_vox_of(double p, int32_t n, double max) {  // get_voxel_cart, grid.f90:51-78
+  const double f = std::floor(((double)n * (p + max)) / (2.0 * max));
+  if (!(f >= 0.0 && f < (double)n)) return -1;
+  return (int32_t)f + 1;
 }
 
 }  // namespace smcrt

@@ -144,6 +144,11 @@ struct ScenePlan {
   // allocation may still veto it (smcrt_scene::lean_ok)
   bool lean_candidate = false;
   bool fold_prio = true, cull_log = false, verbose = false;  // (knobs the device side acts on)
+  // voxel media (plan_voxel_scene): the labels, x fastest; h_props are the media and h_nodes /
+  // h_top hold one placeholder node per medium, so that the optical-property accessors serve both
+  // kinds of scene
+  bool voxel = false;
+  std::vector<uint8_t> labels;
 };
 
 // Validate the scene and decide everything about it that needs no device. Returns SMCRT_OK,
@@ -152,6 +157,19 @@ int plan_scene(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top,
                const smcrt_detector* dets, int32_t n_dets, const Knobs& knobs, const PlanLimits& lim, ScenePlan* out);
 
 TopProps make_props(const smcrt_sdf_node& nd);  // init_mono, opticalProperties.f90:107-125
+
+// A voxel scene (smcrt_voxel_scene_create): validates, and fills what a launch of voxel_kernel
+// needs: grid mode, inv2 / fe, faces, the deposit regime, the media as props. No SDF logic, no
+// lean path. Same return convention as plan_scene.
+int plan_voxel_scene(const uint8_t* labels, const smcrt_medium* media, int32_t n_media, const smcrt_grid* grid,
+                     const smcrt_detector* dets, int32_t n_dets, const Knobs& knobs, ScenePlan* out);
+// The host's restatement of vox_of (transport.h) for smcrt_scene_classify on a voxel scene: the
+// 1-based cell of centred coordinate p on an axis of n cells, -1 outside
+int32_t host_vox_of(double p, int32_t n, double max);
+// Dynamic LDS of voxel_kernel (voxel.h): media + faces, then the deposit words
+inline size_t voxel_lds(const ScenePlan& p, uint32_t dep_words) {
+  return p.face_bytes + (size_t)dep_words * sizeof(uint32_t);
+}
 
 // ---- pure rules of the launch path ----
 // the lean path's dynamic LDS (ws_kernel): staged props + faces, then the block's bucket words

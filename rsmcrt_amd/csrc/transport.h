@@ -107,6 +107,11 @@ struct KCold {
   uint32_t phasor_fixed;      // != 0: every photon's wavenumber is phasor_k (smcrt_phasor_config::fixed_k)
   double* phasor;             // [nx*ny*nz][2]: re, im interleaved, voxel order as jmean
   double phasor_k;            // the fixed wavenumber, or 2 pi / the constant spectrum's wavelength
+  // voxel media (read by voxel_kernel only, voxel.h; null / 0 otherwise). After the phasor fields,
+  // so that those stay where they were.
+  const uint8_t* vox_labels;  // [nx*ny*nz], x fastest as jmean: the medium of each voxel, 0-based
+  uint32_t vox_n_media;       // media in K.props (== K.n_top)
+  uint32_t vox_reserved;
 };
 
 // watchdog sites (KCold::watchdog bits 0-7; smcrt.hip names them)
@@ -463,6 +468,11 @@ struct DdaPiece {
   bool wall = false;  // the piece ended on a voxel wall (ok && !last), the grid's outer walls included
 };
 struct NoDdaPiece {};
+// What voxel_kernel (voxel.h) takes from a crossing: DdaPiece, and the axis update_pos snapped (the
+// first of x, y, z with ldir set: 0, 1, 2), -1 when the piece did not end on a wall.
+struct DdaPieceAxis : DdaPiece {
+  int32_t axis = -1;
+};
 #define LCTR(c) (sh->ctr[(c)][threadIdx.x])
 #define LU(f) (sh->u[(f)][threadIdx.x])
 
@@ -955,6 +965,7 @@ __device__ __forceinline__ void dda_step_r(const KParams& K, S& L, const V3 dir,
   const bool noaxis = !(lx || ly || lz);  // error stop :570-573
   const bool snap = ok && !last && !noaxis;
   const bool snx = lx, sny = !lx && ly, snz = !lx && !ly;
+  if constexpr (std::is_same_v<PC, DdaPieceAxis>) piece->axis = snap ? (snx ? 0 : (sny ? 1 : 2)) : -1;
   // Without a snap the segment ends here and the DDA position is dead, so only the snap
   // case is selected (a zero direction component keeps its coordinate: vx == old.x then).
   const double px = snx && (dir.x > 0.0 || dir.x < 0.0) ? sx : vx;

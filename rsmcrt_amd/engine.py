@@ -17,7 +17,7 @@ import threading
 import numpy as np
 
 from . import abi
-from .scene import detector_array
+from .scene import Mono, VoxelScene, detector_array
 from .tallies import Result
 
 LIB_PATH = os.environ.get("SMCRT_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsmcrt.so")
@@ -44,6 +44,9 @@ def load_library(path: str = LIB_PATH):
         L.smcrt_scene_create.argtypes = [C.POINTER(abi.SdfNode), C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                          C.POINTER(abi.Grid), C.POINTER(abi.Detector), C.c_int32, C.c_int32,
                                          C.POINTER(C.c_void_p)]
+        L.smcrt_voxel_scene_create.argtypes = [C.POINTER(C.c_uint8), C.POINTER(abi.Medium), C.c_int32,
+                                               C.POINTER(abi.Grid), C.POINTER(abi.Detector), C.c_int32, C.c_int32,
+                                               C.POINTER(C.c_void_p)]
         L.smcrt_scene_destroy.argtypes = [C.c_void_p]
         L.smcrt_scene_destroy.restype = None
         L.smcrt_scene_det_bins.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
@@ -56,6 +59,7 @@ def load_library(path: str = LIB_PATH):
         L.smcrt_scene_fence.argtypes = [C.c_void_p, C.c_void_p]
         L.smcrt_scene_check.argtypes = [C.c_void_p]
         L.smcrt_scene_kernel_times.argtypes = [C.c_void_p, C.POINTER(abi.KernelTimes)]
+        L.smcrt_scene_deposit_regime.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.smcrt_normalise_fluence.argtypes = [C.POINTER(C.c_float), C.POINTER(abi.Grid), C.c_uint64]
         L.smcrt_scene_info.argtypes = [C.c_void_p, C.POINTER(abi.Grid), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.smcrt_run_origins.argtypes = [C.c_void_p, C.POINTER(abi.Source), C.POINTER(C.c_double), C.c_int64,
@@ -132,12 +136,19 @@ class Engine:
     def __init__(self, scene, grid, dets=(), device: int = 0):
         L = load_library()
         self.scene, self.grid, self.dets, self.device = scene, grid, list(dets), device
-        self._nodes = scene.node_array()
-        self._top = scene.top_array()
         self._darr = detector_array(self.dets)
         h = C.c_void_p()
-        _check(L.smcrt_scene_create(self._nodes, len(scene.nodes), self._top, scene.n_top, C.byref(grid),
-                                    self._darr, len(self.dets), device, C.byref(h)))
+        if isinstance(scene, VoxelScene):  # a label volume (smcrt_voxel_scene_create)
+            scene.check_grid(grid)
+            self._media = scene.media_array()
+            _check(L.smcrt_voxel_scene_create(scene.labels.ctypes.data_as(C.POINTER(C.c_uint8)), self._media,
+                                              scene.n_media, C.byref(grid), self._darr, len(self.dets), device,
+                                              C.byref(h)))
+        else:
+            self._nodes = scene.node_array()
+            self._top = scene.top_array()
+            _check(L.smcrt_scene_create(self._nodes, len(scene.nodes), self._top, scene.n_top, C.byref(grid),
+                                        self._darr, len(self.dets), device, C.byref(h)))
         self._h = h
 
     def close(self):
@@ -215,6 +226,27 @@ class Engine:
                                                    kap.ctypes.data_as(C.POINTER(C.c_double))))
         return lay, kap
 
+    def voxelise(self, outside=None) -> VoxelScene:
+        """This SDF scene as a label volume on the engine's grid: the label of a voxel is the layer
+        `classify` gives its centre, minus 1, and medium i is the optics of top-level SDF i. Voxels
+        whose centre lies in no SDF get the medium `outside` (a `scene.mono(...)`), appended last;
+        without `outside` such a voxel raises ValueError. Engine(eng.voxelise(), grid, dets) then
+        runs the scene's voxel twin."""
+        if isinstance(self.scene, VoxelScene):
+            raise ValueError("voxelise() is for an SDF scene; this engine already runs a voxel scene")
+        g = self.grid
+        cx, cy, cz = [(np.arange(n) + 0.5) * (2.0 * m / n) - m for n, m in ((g.nx, g.xmax), (g.ny, g.ymax), (g.nz, g.zmax))]
+        pts = np.stack(np.meshgrid(cz, cy, cx, indexing="ij")[::-1], axis=-1).reshape(-1, 3)  # x fastest
+        lay, _ = self.classify(pts)
+        media = [Mono(float(o.mus), float(o.mua), float(o.hgg), float(o.n)) for o in (s.opt for s in self.scene.sdfs)]
+        if np.any(lay == 0):
+            if outside is None:
+                i = int(np.flatnonzero(lay == 0)[0])
+                raise ValueError(f"the centre of voxel {i} (x fastest) {tuple(pts[i])} lies in no SDF: pass `outside`")
+            media.append(outside)
+            lay = np.where(lay == 0, len(media), lay)
+        return VoxelScene((lay - 1).astype(np.uint8), media)
+
     def escape(self, cfg: abi.EscapeConfig, n_photons, source=None, seed=123456789, flags=abi.FLAG_PATHLENGTH,
                result: Result | None = None):
         """The escape function (smcrt_escape_run): (escape_sym (n_dets, n0, n1, n2), escape
@@ -284,6 +316,13 @@ class Engine:
         return {"transport_ms": t.transport_ms, "deposit_ms": t.deposit_ms, "launches": t.launches,
                 "lean_launches": t.lean_launches, "far_steps": t.far_steps,
                 "fold_cu_ms": t.fold_cu_ms, "lean_hazards": t.lean_hazards}
+
+    def deposit_regime(self) -> str:
+        """How the scene's plan files the jmean deposits of a path-length run with unit weights:
+        "buckets", "sorted" or "atomic" (smcrt_scene_deposit_regime; SMCRT_DEPOSIT at creation)."""
+        r = C.c_int32()
+        _check(load_library().smcrt_scene_deposit_regime(self._h, C.byref(r)))
+        return abi.DEPOSIT_REGIMES[r.value]
 
     def set_path_tracking(self, range_first=0, range_count=0, max_vertices=64, max_paths=65536):
         """Configure photon-path recording (smcrt_scene_set_path_tracking): runs made with

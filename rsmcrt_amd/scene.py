@@ -409,6 +409,50 @@ class Scene:
         return (C.c_int32 * len(self.top))(*self.top)
 
 
+class VoxelScene:
+    """A label volume and its table of media (smcrt_voxel_scene_create): `labels` is an array of
+    shape (nx, ny, nz), or flat with x fastest (the order of Result.jmean), of 0-based indices
+    into `media`, a list of optical properties (`mono(...)`). Engine(voxel_scene, grid, dets)
+    runs it; the grid's nx, ny, nz must be the labels' shape."""
+
+    def __init__(self, labels, media):
+        a = np.asarray(labels)
+        if a.ndim not in (1, 3):
+            raise ValueError(f"labels must have shape (nx, ny, nz) or be flat with x fastest, not {a.shape}")
+        if a.size == 0:
+            raise ValueError("labels is empty")
+        if not np.issubdtype(a.dtype, np.integer) and not np.all(a == np.floor(a)):
+            raise ValueError("labels must be whole numbers")
+        self.media = list(media)
+        if not 1 <= len(self.media) <= 256:
+            raise ValueError(f"a voxel scene takes 1 .. 256 media, not {len(self.media)}")
+        if a.min() < 0 or a.max() > 255:
+            raise ValueError("labels must lie in 0 .. 255")
+        self.shape = tuple(a.shape) if a.ndim == 3 else None
+        # (nx, ny, nz) indexed [i, j, k] -> x fastest
+        self.labels = np.ascontiguousarray((a.transpose(2, 1, 0) if a.ndim == 3 else a).astype(np.uint8)).ravel()
+
+    @property
+    def n_media(self) -> int:
+        return len(self.media)
+
+    def check_grid(self, g) -> None:
+        if self.shape is not None and self.shape != (g.nx, g.ny, g.nz):
+            raise ValueError(f"labels of shape {self.shape} on a grid of {(g.nx, g.ny, g.nz)}")
+        if self.labels.size != g.nx * g.ny * g.nz:
+            raise ValueError(f"{self.labels.size} labels on a grid of {g.nx * g.ny * g.nz} voxels")
+
+    def volume(self, g):
+        """The labels as an (nx, ny, nz) array."""
+        return self.labels.reshape(g.nz, g.ny, g.nx).transpose(2, 1, 0)
+
+    def media_array(self):
+        arr = (abi.Medium * len(self.media))()
+        for i, o in enumerate(self.media):
+            arr[i].mus, arr[i].mua, arr[i].hgg, arr[i].n = float(o.mus), float(o.mua), float(o.hgg), float(o.n)
+        return arr
+
+
 # ------------------------------------------------------------------ grid ----------
 def grid(nx, ny, nz, xmax, ymax, zmax) -> abi.Grid:
     g = abi.Grid()
