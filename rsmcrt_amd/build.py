@@ -20,7 +20,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 LIB = os.path.join(PKG, "libsmcrt.so")
 SOURCES = [os.path.join(PKG, "csrc", f) for f in ("smcrt.hip", "writers.cpp", "frontend.cpp", "sources.cpp", "png.cpp", "escape.cpp", "inverse.cpp", "spectral.cpp", "multi.hip", "cull.cpp", "sceneplan.cpp", "dispexpr.cpp")]
-# the transport kernel instantiations: kinst.hip once per (LDS faces, grid mode), kernel_ptrs.h
+# the transport kernel instantiations: kinst.hip once per (LDS faces, grid mode, part), kernel_ptrs.h
 KINST = os.path.join(PKG, "csrc", "kinst.hip")
 # Part 1 (the plain ws_kernel, M1's lean path) schedules with the AMDGPU register-pressure
 # trackers: M1 259.0/260.2 vs 257.8/257.3 M photons/s same box, while the XF ws_kernel (M3)
@@ -34,7 +34,13 @@ UNITS = [(src, ()) for src in SOURCES] + [
     # part 3: transport_kernel's phasor tally (PHAS, faces in device memory only)
     (KINST, ("-DKI_F=0", f"-DKI_G={g}", "-DKI_P=3")) for g in (0, 1, 2)] + [
     # part 4: voxel_kernel (voxel.h: label volumes; its faces are always staged in LDS)
-    (KINST, ("-DKI_F=0", f"-DKI_G={g}", "-DKI_P=4")) for g in (0, 1, 2)]
+    (KINST, ("-DKI_F=0", f"-DKI_G={g}", "-DKI_P=4")) for g in (0, 1, 2)] + [
+    # parts 5 and 6: ws_kernel for SMCRT_FLAG_TEST_KERNEL runs (TK in ws.h), plain and XF, each with
+    # the scheduler flags of the part it came from (1 and 0). Twelve more units, 45 in all; a clean
+    # build on 8 cores took 1 min 43 s against 1 min 47 s before (11.7 against 10.9 min of CPU
+    # time): parts 0 and 1 compile a shorter ws_kernel, which pays for most of the new units.
+    (KINST, (f"-DKI_F={f}", f"-DKI_G={g}", f"-DKI_P={p}") + (PLAIN_WS_FLAGS if p == 5 else ()))
+    for f in (0, 1) for g in (0, 1, 2) for p in (5, 6)]
 DEPS = SOURCES + [KINST] + sorted(glob.glob(os.path.join(PKG, "csrc", "*.h"))) + [os.path.join(ROOT, "include", "smcrt.h")]
 ARCH = os.environ.get("SMCRT_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=off: no fused multiply-add, so fp64 trajectories are bit-identical to the

@@ -1,7 +1,8 @@
 // kernel_ptrs.h — the transport kernel instantiations, reached through pointers.
 //
 // build.py compiles kinst.hip once per (LDS faces F, grid mode G, part P) with -DKI_F=F -DKI_G=G
-// -DKI_P=P (part 1: the plain ws_kernel, with its own scheduler flags; part 2, F = 0 only:
+// -DKI_P=P (part 1: the plain ws_kernel, with its own scheduler flags; parts 5 and 6: the plain
+// and the XF ws_kernel of test_kernel runs, TK = true in ws.h; part 2, F = 0 only:
 // transport_kernel's HIST instantiations, the photon path recorder of paths.h; part 3, F = 0
 // only: its PHAS instantiations, the phasor tally of phasor.h; part 4, F = 0 only: voxel_kernel,
 // the label-volume transport of voxel.h), so
@@ -20,8 +21,12 @@ size_t kinst_ws_scratch_bytes(size_t lanes);  // ws_kernel lane scratch (ws.h WX
 
 #define SMCRT_KINST_DECL(F, G)                                                               \
   const void* kinst_transport_##F##_##G(int xsrc, int coop);                                 \
-  const void* kinst_ws_##F##_##G(int xf, int slots);                                         \
+  const void* kinst_ws_##F##_##G(int xf, int slots, int tk);                                 \
   const void* kinst_wsp_##F##_##G(int slots);                                                \
+  const void* kinst_wspt_##F##_##G(int slots);                                               \
+  const void* kinst_wsxt_##F##_##G(int xf, int slots);                                       \
+  void kinst_diagpt_##F##_##G(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6); \
+  void kinst_diagxt_##F##_##G(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6); \
   void kinst_diag_##F##_##G(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6); \
   void kinst_diagp_##F##_##G(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6);
 SMCRT_KINST_DECL(0, 0)
@@ -79,17 +84,18 @@ inline const void* voxel_kernel_ptr(int gm, bool xsrc) {
   const int x = xsrc ? 1 : 0;
   return gm == 0 ? kinst_voxel_0_0(x) : gm == 1 ? kinst_voxel_0_1(x) : kinst_voxel_0_2(x);
 }
-// ws_kernel<lds_faces, gm, xf, slots, iv> (xf: the Fresnel/detector program points; slots 2 or 3;
-// iv: the in-voxel segments' code, always in the plain instantiation, ws.h)
-inline const void* ws_kernel_ptr(bool lds_faces, int gm, bool xf, int slots, bool iv) {
-  const int x = xf ? (iv ? 2 : 1) : 0;
+// ws_kernel<lds_faces, gm, xf, slots, iv, tk> (xf: the Fresnel/detector program points; slots 2 or
+// 3; iv: the in-voxel segments' code, always in the plain instantiation; tk: a run with
+// SMCRT_FLAG_TEST_KERNEL, every other run takes the instantiation without its event code, ws.h)
+inline const void* ws_kernel_ptr(bool lds_faces, int gm, bool xf, int slots, bool iv, bool tk) {
+  const int x = xf ? (iv ? 2 : 1) : 0, t = tk ? 1 : 0;
   switch ((lds_faces ? 3 : 0) + gm) {
-    case 0: return kinst_ws_0_0(x, slots);
-    case 1: return kinst_ws_0_1(x, slots);
-    case 2: return kinst_ws_0_2(x, slots);
-    case 3: return kinst_ws_1_0(x, slots);
-    case 4: return kinst_ws_1_1(x, slots);
-    default: return kinst_ws_1_2(x, slots);
+    case 0: return kinst_ws_0_0(x, slots, t);
+    case 1: return kinst_ws_0_1(x, slots, t);
+    case 2: return kinst_ws_0_2(x, slots, t);
+    case 3: return kinst_ws_1_0(x, slots, t);
+    case 4: return kinst_ws_1_1(x, slots, t);
+    default: return kinst_ws_1_2(x, slots, t);
   }
 }
 // diagnostic builds: the kernels' tallies summed over the objects (each is cleared)
@@ -101,6 +107,10 @@ inline void kinst_diag_gather(unsigned long long* d72, unsigned long long* t9, u
   kinst_diag_1_0(d72, t9, c6); kinst_diag_1_1(d72, t9, c6); kinst_diag_1_2(d72, t9, c6);
   kinst_diagp_0_0(d72, t9, c6); kinst_diagp_0_1(d72, t9, c6); kinst_diagp_0_2(d72, t9, c6);
   kinst_diagp_1_0(d72, t9, c6); kinst_diagp_1_1(d72, t9, c6); kinst_diagp_1_2(d72, t9, c6);
+  kinst_diagpt_0_0(d72, t9, c6); kinst_diagpt_0_1(d72, t9, c6); kinst_diagpt_0_2(d72, t9, c6);
+  kinst_diagpt_1_0(d72, t9, c6); kinst_diagpt_1_1(d72, t9, c6); kinst_diagpt_1_2(d72, t9, c6);
+  kinst_diagxt_0_0(d72, t9, c6); kinst_diagxt_0_1(d72, t9, c6); kinst_diagxt_0_2(d72, t9, c6);
+  kinst_diagxt_1_0(d72, t9, c6); kinst_diagxt_1_1(d72, t9, c6); kinst_diagxt_1_2(d72, t9, c6);
   kinst_diagh_0_0(d72, t9, c6); kinst_diagh_0_1(d72, t9, c6); kinst_diagh_0_2(d72, t9, c6);
   kinst_diagf_0_0(d72, t9, c6); kinst_diagf_0_1(d72, t9, c6); kinst_diagf_0_2(d72, t9, c6);
   kinst_diagv_0_0(d72, t9, c6); kinst_diagv_0_1(d72, t9, c6); kinst_diagv_0_2(d72, t9, c6);

@@ -1,12 +1,15 @@
 // kinst.hip — one (LDS faces, grid mode) slice of the transport kernel instantiations.
-// Compiled twenty-one times by build.py (-DKI_F=0/1 -DKI_G=0/1/2 -DKI_P=0/1, and -DKI_P=2, 3 and 4
-// with -DKI_F=0); see kernel_ptrs.h.
+// Compiled thirty-three times by build.py (-DKI_F=0/1 -DKI_G=0/1/2 -DKI_P=0/1/5/6, and -DKI_P=2, 3
+// and 4 with -DKI_F=0); see kernel_ptrs.h.
 // Part 0 holds transport_kernel and the XF ws_kernel, part 1 the plain ws_kernel (the lean path
 // of M1), which build.py compiles with its own scheduler flags (see UNITS there), part 2 the
 // HIST instantiations of transport_kernel (the photon path recorder, paths.h; faces in device
 // memory only), in units of their own so that they build beside the others, part 3 likewise the
 // PHAS instantiations (the phasor tally, phasor.h). Nothing is instantiated for PHAS && HIST.
 // Part 4 holds voxel_kernel (voxel.h: label volumes, no SDF), plain and general emitter.
+// Parts 5 and 6 hold ws_kernel's TK = true instantiations (SMCRT_FLAG_TEST_KERNEL runs, ws.h), the
+// plain ones (5, with part 1's scheduler flags) and the XF ones (6, with part 0's), in units of
+// their own so that they build beside the others.
 #include "kernels.h"
 #include "kernel_ptrs.h"
 #if defined(KI_P) && KI_P == 4
@@ -14,7 +17,7 @@
 #endif
 
 #if !defined(KI_F) || !defined(KI_G) || !defined(KI_P)
-#error "kinst.hip is compiled with -DKI_F=<0|1> -DKI_G=<0|1|2> -DKI_P=<0|1|2|3|4> (rsmcrt_amd/build.py)"
+#error "kinst.hip is compiled with -DKI_F=<0|1> -DKI_G=<0|1|2> -DKI_P=<0|1|2|3|4|5|6> (rsmcrt_amd/build.py)"
 #endif
 #define KI_NAME3(a, f, g) a##_##f##_##g
 #define KI_NAME2(a, f, g) KI_NAME3(a, f, g)
@@ -52,11 +55,28 @@ const void* KI_NAME(kinst_transport_hist)(int xsrc, int coop) {
   return (const void*)transport_kernel<false, KI_G, false, false, true>;
 }
 #define KI_DIAG_NAME KI_NAME(kinst_diagh)
+#elif KI_P == 6
+// the XF ws_kernel of test_kernel runs (xf 2: with the in-voxel segments' code)
+const void* KI_NAME(kinst_wsxt)(int xf, int slots) {
+  if (xf == 2)
+    return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, true, 3, true, true>
+                      : (const void*)ws_kernel<KI_F != 0, KI_G, true, 2, true, true>;
+  return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, true, 3, false, true>
+                    : (const void*)ws_kernel<KI_F != 0, KI_G, true, 2, false, true>;
+}
+#define KI_DIAG_NAME KI_NAME(kinst_diagxt)
+#elif KI_P == 5
+// the plain ws_kernel of test_kernel runs
+const void* KI_NAME(kinst_wspt)(int slots) {
+  return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, false, 3, true, true>
+                    : (const void*)ws_kernel<KI_F != 0, KI_G, false, 2, true, true>;
+}
+#define KI_DIAG_NAME KI_NAME(kinst_diagpt)
 #elif KI_P == 1
 // the plain ws_kernel (no Fresnel program points, no detectors)
 const void* KI_NAME(kinst_wsp)(int slots) {
-  return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, false, 3, true>
-                    : (const void*)ws_kernel<KI_F != 0, KI_G, false, 2, true>;
+  return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, false, 3, true, false>
+                    : (const void*)ws_kernel<KI_F != 0, KI_G, false, 2, true, false>;
 }
 #define KI_DIAG_NAME KI_NAME(kinst_diagp)
 #else
@@ -78,13 +98,15 @@ int kinst_ws_photon_lanes() { return (int)WS_NPL; }
 size_t kinst_ws_scratch_bytes(size_t lanes) { return ws_scratch_bytes(lanes); }
 #endif
 
-const void* KI_NAME(kinst_ws)(int xf, int slots) {  // xf 2: the XF instantiation with the in-voxel segments' code
+// xf 2: the XF instantiation with the in-voxel segments' code; tk: a test_kernel run (parts 5 and 6)
+const void* KI_NAME(kinst_ws)(int xf, int slots, int tk) {
+  if (tk) return xf ? KI_NAME(kinst_wsxt)(xf, slots) : KI_NAME(kinst_wspt)(slots);
   if (xf == 2)
-    return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, true, 3, true>
-                      : (const void*)ws_kernel<KI_F != 0, KI_G, true, 2, true>;
+    return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, true, 3, true, false>
+                      : (const void*)ws_kernel<KI_F != 0, KI_G, true, 2, true, false>;
   if (xf)
-    return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, true, 3, false>
-                      : (const void*)ws_kernel<KI_F != 0, KI_G, true, 2, false>;
+    return slots == 3 ? (const void*)ws_kernel<KI_F != 0, KI_G, true, 3, false, false>
+                      : (const void*)ws_kernel<KI_F != 0, KI_G, true, 2, false, false>;
   return KI_NAME(kinst_wsp)(slots);
 }
 #define KI_DIAG_NAME KI_NAME(kinst_diag)

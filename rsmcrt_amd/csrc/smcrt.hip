@@ -375,8 +375,9 @@ static void size_grids(smcrt_scene* s) {
   s->lean_ok = s->lean_candidate;
   const bool xf = s->fresnel || s->n_dets > 0;
   if (s->lean_ok) {
+    // (the test_kernel instantiation has the same block, LDS and register cap: one grid for both)
     hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, ws_kernel_ptr(s->lds_faces, s->grid_mode, xf, s->ws_slots, ws_invoxel_on(s->ws_invoxel, xf)),
+        &per_cu, ws_kernel_ptr(s->lds_faces, s->grid_mode, xf, s->ws_slots, ws_invoxel_on(s->ws_invoxel, xf), false),
         kinst_ws_threads(), lean_lds(*s));
     if (oe != hipSuccess || per_cu < 1) per_cu = 1;
     s->grid_blocks_ws = cus * per_cu;
@@ -684,7 +685,8 @@ static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xs
     ++s->lean_launches;
     void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&C};
     const bool xf = s->d_lscratch != nullptr;
-    HIPCHK(hipLaunchKernel(ws_kernel_ptr(s->lds_faces, s->grid_mode, xf, s->ws_slots, ws_invoxel_on(s->ws_invoxel, xf)),
+    const bool tk = (K.flags & SMCRT_FLAG_TEST_KERNEL) != 0;
+    HIPCHK(hipLaunchKernel(ws_kernel_ptr(s->lds_faces, s->grid_mode, xf, s->ws_slots, ws_invoxel_on(s->ws_invoxel, xf), tk),
                            dim3(blocks), dim3(kinst_ws_threads()), args, lean_lds(*s), stream));
   } else {
     const smcrt_detector* a_dets = K.dets;
@@ -763,10 +765,10 @@ static int diag_report(hipStream_t stream, bool lean) {
     std::fprintf(stderr, "[diag-ws] walker iters %llu: idle %.3f, busy lanes/iter %.1f, pending lanes/iter %.1f | "
                  "photon trips %llu: sleep %.3f, idle lanes %.1f, sync-waiting %.2f, slot-blocked %.2f, EVAL lanes "
                  "%.1f, pushes %.2f, P7 runs %.3f (lanes/run %.1f), event-waiting %.2f | producer waits %llu | event "
-                 "iters %llu, lanes/iter %.1f\n",
+                 "iters %llu, lanes/iter %.1f | emissions waiting for a slot %llu lane-trips\n",
                  h[20], h[21] / wi, h[22] / wi, h[23] / wi, h[24], h[25] / pt, h[30] / pt, h[27] / pt, h[26] / pt,
                  h[31] / pt, h[32] / pt, h[28] / pt, (double)h[29] / (double)std::max(1ull, h[28]), h[36] / pt, h[33],
-                 h[34], (double)h[35] / (double)std::max(1ull, h[34]));
+                 h[34], (double)h[35] / (double)std::max(1ull, h[34]), h[51]);
     // region times (ws.h WST): shares of each role's wave time
     const char* np[8] = {"fetch", "poll", "eval", "p3p4", "handout", "p5p6", "p7", "p8"};
     double tp = 0, tw = 0, te = 0;

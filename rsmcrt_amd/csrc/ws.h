@@ -27,7 +27,8 @@
 //     event on the owner's values with the owner's own Philox stream and writes the results
 //     back, so the event code runs on full waves. Completion, the rare terminal interactions
 //     and every event of test_kernel runs (moments) stay in the photon waves, batched once
-//     SMCRT_LEAN_EVENT_LANES lanes wait.
+//     SMCRT_LEAN_EVENT_LANES lanes wait (test_kernel runs have an instantiation of their own,
+//     see "Production runs").
 // A segment's walk is a pure function of (start, direction, length) (the start cell is
 // recomputed from the start with the same cell_of) and the deferred/synchronous rule and the
 // hazard accounting are lean.h's, so the records, counters and tallies are transport_kernel's;
@@ -76,6 +77,25 @@
 // deferred segment writes later is not read (ST_ABSORB and the record read a slot's word only
 // without LF_CELLS, and the next handed-out segment clears it as before). The path adds no
 // cross-wave wait, so the watchdog sites and the termination argument above are unchanged.
+//
+// Production runs (the template parameter TK). A run with SMCRT_FLAG_TEST_KERNEL keeps every
+// event in the photon waves (TK = true: the code as described above). Every other run takes the
+// TK = false instantiation, whose photon waves hold neither that event code nor the RNG:
+//   * the batched P7 block is only the terminal interactions (tflag or fault, the
+//     MAX_INTERACTIONS stop) and completion; an interaction that draws, a tauint2 entry and an
+//     emission always go to the event waves;
+//   * a fetched photon whose slot P.seq is still busy (a deferred segment of the lane's previous
+//     photon is still being walked) stays in ST_EMIT and queues its emission on a later trip.
+//     The slot is freed by the walker that holds its segment, and no walker waits for a photon
+//     (a walker waits only for bucket claims among walkers), so this wait closes no cycle: it is
+//     the wait of a hand-out for its slot. It counts among the states in which "every photon
+//     of the wave waits", so the wave yields and the watchdog covers it;
+//   * the photon's RNG state lives in its event slot only: the lane writes ev_pid, ev_draws = 0
+//     and ev_cached (Rng::init's values) at fetch, the event lanes advance ev_draws and
+//     ev_cached as before (written before the release store of ev_code, which the photon reads
+//     with acquire), and completion reads ev_draws (and ev_pid for a photon record) from LDS.
+//     The poll and the enqueue copy neither.
+// The plan, the slots, the LDS layout and the counters are the same for both.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -102,6 +122,11 @@ namespace smcrt {
 // the plain instantiation reads the deferral box from KParams too (1) or keeps it in VGPRs (0)
 #ifndef SMCRT_WS_KBOUNDS_PLAIN
 #define SMCRT_WS_KBOUNDS_PLAIN 0
+#endif
+// the photon waves' EVAL takes top-level spheres and boxes two at a time (1; transport.h
+// eval_sdfs PAIRS) or one by one (0)
+#ifndef SMCRT_WS_EVAL_PAIRS
+#define SMCRT_WS_EVAL_PAIRS 0
 #endif
 #ifndef SMCRT_WS_START_CELLS
 #define SMCRT_WS_START_CELLS 1
@@ -210,7 +235,9 @@ enum : int { WD_WITERS = 20, WD_WIDLE, WD_WBUSY, WD_WPEND, WD_PTRIPS, WD_PSLEEP,
              WD_P7LANES, WD_PIDLE, WD_ELANES, WD_PUSH, WD_PRODWAIT, WD_EITERS, WD_ELANESRUN, WD_PEVQ,
              // s_memtime ticks per region (WST): photon waves, walker waves, event waves
              WD_TP_FETCH, WD_TP_POLL, WD_TP_EVAL, WD_TP_P34, WD_TP_HAND, WD_TP_P56, WD_TP_P7, WD_TP_P8,
-             WD_TW_CLAIM, WD_TW_IDLE, WD_TW_WALK, WD_TW_FIN, WD_TE_RUN, WD_TE_IDLE, WD_N };
+             WD_TW_CLAIM, WD_TW_IDLE, WD_TW_WALK, WD_TW_FIN, WD_TE_RUN, WD_TE_IDLE,
+             WD_PEMITW,  // lanes whose emission waited for its slot (!TK), per trip
+             WD_N };
 static_assert(WD_N <= 64, "g_diag[64..] belongs to transport_kernel");
 #define WSDIAG(i, v) (wd[(i) - WD_WITERS] += (uint64_t)(v))
 #define WST(i)                                                \
@@ -231,7 +258,9 @@ static_assert(WD_N <= 64, "g_diag[64..] belongs to transport_kernel");
 // the binding role and short of registers, so the code costs it 5 % switched off (scratch 116
 // -> 140 B) and 11 % switched on (M3 158.6-163.0 and 172.3-172.8 vs 181.0-181.8 M photons/s,
 // profiles/r07_invoxel/ab_invoxel.txt); XF scenes run IV only with SMCRT_WS_INVOXEL=1.
-template <bool LDS_FACES, int GM, bool XF, uint32_t SL, bool IV>
+// TK: the run has SMCRT_FLAG_TEST_KERNEL (see "Production runs" in the header); false for every
+// other run, whose photon waves then hold no inline event code and no RNG state.
+template <bool LDS_FACES, int GM, bool XF, uint32_t SL, bool IV, bool TK>
 __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void ws_kernel(
     KParams K, const smcrt_sdf_node* __restrict__ nodes, const ProgOp* __restrict__ prog,
     const KCold* __restrict__ C) {
@@ -294,7 +323,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
   if (wv < WS_PW) {
     WS_MARK(1);
     // =================================================================== photon waves ======
-    const bool test_kernel = (K.flags & SMCRT_FLAG_TEST_KERNEL) != 0;
+    const bool test_kernel = TK && (K.flags & SMCRT_FLAG_TEST_KERNEL) != 0;
     const bool records_on = (K.flags & SMCRT_FLAG_RECORD_PHOTONS) != 0 && C->records != nullptr;
     const uint32_t pl = threadIdx.x;  // photon lane (the photon waves come first)
 #define WLU(f) (sh->lu[(f)][pl])
@@ -378,8 +407,15 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
           const uint32_t take = n < chunk_left ? n : chunk_left;
           const uint64_t rank = __popcll(need & ((1ull << lane_id) - 1ull));
           if (P.st == ST_FETCH && rank < take) {
-            P.rng.init(C->first_photon + chunk_base + rank);
-            sh->ev_pid[0][pl] = P.rng.pid_lo; sh->ev_pid[1][pl] = P.rng.pid_hi;  // (the event lanes' key)
+            if constexpr (TK) {
+              P.rng.init(C->first_photon + chunk_base + rank);
+              sh->ev_pid[0][pl] = P.rng.pid_lo; sh->ev_pid[1][pl] = P.rng.pid_hi;  // (the event lanes' key)
+            } else {  // the whole RNG state lives in the event slot (Rng::init's values)
+              const uint64_t pid = C->first_photon + chunk_base + rank;
+              sh->ev_pid[0][pl] = (uint32_t)pid; sh->ev_pid[1][pl] = (uint32_t)(pid >> 32);
+              sh->ev_draws[pl] = 0u;
+              sh->ev_cached[pl] = 0.0;
+            }
             P.st = ST_EMIT;
           }
           chunk_base += take;
@@ -396,8 +432,10 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
         const uint32_t code = __hip_atomic_load(&sh->ev_code[pl], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (code & EV_DONE) {
           P.clr(LF_EVQ);
-          P.rng.draws = sh->ev_draws[pl];
-          P.rng.cached = sh->ev_cached[pl];
+          if constexpr (TK) {
+            P.rng.draws = sh->ev_draws[pl];
+            P.rng.cached = sh->ev_cached[pl];
+          }
           if (P.st == ST_EMIT) {  // the emitted photon (its tauint2 entry follows the layer search)
             P.pos = v3(sh->seg[P.seq][SG_OX][pl], sh->seg[P.seq][SG_OY][pl], sh->seg[P.seq][SG_OZ][pl]);
             P.dir = v3(sh->ev_dir[0][pl], sh->ev_dir[1][pl], sh->ev_dir[2][pl]);
@@ -455,6 +493,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
       WSDIAG(WD_PIDLE, __popcll(__ballot(P.st == ST_IDLE)));
       WSDIAG(WD_PWAIT, __popcll(__ballot(P.has(LF_WAIT))));
       WSDIAG(WD_PEVQ, __popcll(__ballot(P.has(LF_EVQ))));
+      WSDIAG(WD_PEMITW, __popcll(__ballot(!TK && P.st == ST_EMIT && !P.has(LF_EVQ) && (ws_busy(sh, pl) & (1u << P.seq)))));
 
       WST(WD_TP_POLL);
       // ---- EVAL: the SDF array at the photon's query point ------------------------------------
@@ -464,7 +503,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
       if (__ballot(have)) {
         const bool mask_le = test_kernel && P.st == ST_LAYER;
         const V3 q = (P.st == ST_H1 || P.st == ST_G0) ? P.pos + smul(P.d, P.dir) : P.pos;
-        R = eval_sdfs(nodes, prog, K.n_prog, q, mask_le, 0, 0);
+        R = eval_sdfs<false, SMCRT_WS_EVAL_PAIRS != 0>(nodes, prog, K.n_prog, q, mask_le, 0, 0);
         const bool counted = P.st == ST_H0 || P.st == ST_H1 || P.st == ST_H3 || P.st == ST_M1 || P.st == ST_G0;
         w_sdf += __popcll(__ballot(have && counted)) * (uint32_t)K.n_top;
         WSDIAG(WD_ELANES, __popcll(__ballot(have)));
@@ -766,8 +805,10 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
               else if (watchdog_expired(C, t0, WDOG_EVENT_QUEUE)) break;
             }
             sh->ev_dir[0][pl] = P.dir.x; sh->ev_dir[1][pl] = P.dir.y; sh->ev_dir[2][pl] = P.dir.z;
-            sh->ev_cached[pl] = P.rng.cached;
-            sh->ev_draws[pl] = P.rng.draws;
+            if constexpr (TK) {
+              sh->ev_cached[pl] = P.rng.cached;
+              sh->ev_draws[pl] = P.rng.draws;
+            }
             if (XF && P.st == ST_F0) {  // reflect_refract's inputs: pos and step in the free slot, the new layer
               sh->seg[P.seq][SG_OX][pl] = P.pos.x; sh->seg[P.seq][SG_OY][pl] = P.pos.y;
               sh->seg[P.seq][SG_OZ][pl] = P.pos.z; sh->seg[P.seq][SG_LEN][pl] = P.d;
@@ -789,10 +830,14 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
       }
       // ---- P7: the photon's other events, batched ---------------------------------------------
       {
+        // (!TK: the block above queued every interaction that draws, every tauint2 entry and
+        // every emission whose slot was free, so what is left of ST_INTERACT is terminal; an
+        // emission that waits for its slot is no event and holds no batch back)
         const bool ev = free_ && !P.has(LF_EVQ) &&
-                        (P.st == ST_INTERACT || P.st == ST_T2 || P.st == ST_EMIT || P.st == ST_DONE);
+                        (P.st == ST_INTERACT || P.st == ST_DONE || (TK && (P.st == ST_T2 || P.st == ST_EMIT)));
         const uint64_t evm = __ballot(ev);
-        const uint64_t busy = __ballot(P.st != ST_IDLE && P.st != ST_FETCH && !P.has(LF_EVQ));
+        const uint64_t busy = __ballot(P.st != ST_IDLE && P.st != ST_FETCH && !P.has(LF_EVQ) &&
+                                       (TK || P.st != ST_EMIT));
         const uint32_t nev = __popcll(evm);
         // (test_kernel runs every event here; otherwise only emission, completion and the rare
         // terminal interactions are left, one or two per photon: run them once a few wait)
@@ -807,7 +852,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             } else if (WLU(LL_INTER) + 1u > (uint32_t)MAX_INTERACTIONS) {
               ++WLU(LL_INTER);
               P.set(LF_FAULT); P.st = ST_DONE;
-            } else {
+            } else if constexpr (TK) {
               const double ran = P.rng.next(K.key0, K.key1);
               const TopProps pr = props[P.layer - 1];
               const bool sc = ran < pr.albedo;
@@ -844,7 +889,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
               }
             }
           }
-          if (ev && P.st == ST_T2) {  // tauint2 entry, inttau2.f90:48-60
+          if (TK && ev && P.st == ST_T2) {  // tauint2 entry, inttau2.f90:48-60
             ++r_tau;
             t2_entry();
             P.tau = -det_log(P.rng.next(K.key0, K.key1));
@@ -852,7 +897,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             P.hop = 0;
             P.st = ST_H0;  // arrives in P8
           }
-          if (ev && P.st == ST_EMIT) {  // kernelsMod.f90:1937-1945
+          if (TK && ev && P.st == ST_EMIT) {  // kernelsMod.f90:1937-1945
             P.clr(LF_FAULT); P.layer = 0;
             WLU(LL_STATUS) = 0; WLU(LL_NSCATT) = 0; WLU(LL_INTER) = 0;
             if constexpr (XF) XI[WXI_BOUNCES * xs] = 0;
@@ -880,14 +925,21 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             if (P.has(LF_FAULT)) { WLU(LL_STATUS) = 3; ws_count(sh, LC_FAULTS); }
             else if (WLU(LL_STATUS) == 0) { WLU(LL_STATUS) = 2; ws_count(sh, LC_ESCAPED); }
             ws_count(sh, LC_PHOTONS);
-            atomicAdd(&sh->wctr[wv][LC_DRAWS], P.rng.draws);
+            // (!TK: the event lanes left the photon's draws in its event slot, before the release
+            // of the ev_code that this lane has read with acquire; the index words are its own)
+            const uint32_t draws = TK ? P.rng.draws : sh->ev_draws[pl];
+            atomicAdd(&sh->wctr[wv][LC_DRAWS], draws);
             iv_flush();  // (the photon's last in-voxel deposits)
 #ifdef SMCRT_DIAG
-            if (C->done_time)
-              C->done_time[(((uint64_t)P.rng.pid_hi << 32) | P.rng.pid_lo) - C->done_base] = __builtin_amdgcn_s_memrealtime();
+            if (C->done_time) {
+              const uint64_t dp = TK ? ((uint64_t)P.rng.pid_hi << 32) | P.rng.pid_lo
+                                     : ((uint64_t)sh->ev_pid[1][pl] << 32) | sh->ev_pid[0][pl];
+              C->done_time[dp - C->done_base] = __builtin_amdgcn_s_memrealtime();
+            }
 #endif
             if (records_on) {
-              const uint64_t pid = ((uint64_t)P.rng.pid_hi << 32) | P.rng.pid_lo;
+              const uint64_t pid = TK ? ((uint64_t)P.rng.pid_hi << 32) | P.rng.pid_lo
+                                      : ((uint64_t)sh->ev_pid[1][pl] << 32) | sh->ev_pid[0][pl];
               smcrt_photon_record* r = C->records + (pid - C->first_photon);
               r->pos[0] = P.pos.x; r->pos[1] = P.pos.y; r->pos[2] = P.pos.z;
               r->dir[0] = P.dir.x; r->dir[1] = P.dir.y; r->dir[2] = P.dir.z;
@@ -896,7 +948,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
               r->layer = P.layer;
               r->nscatt = WLU(LL_NSCATT);
               r->bounces = XF ? XI[WXI_BOUNCES * xs] : 0u;
-              r->draws = P.rng.draws;
+              r->draws = draws;
               r->status = WLU(LL_STATUS);
             }
             P.clr(LF_TFLAG | LF_FAULT);
@@ -909,9 +961,10 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
       // ---- P8: arrive at the hop-loop head, :61 ---------------------------------------------
       p8();
       // every photon of the wave waits for a walker (a synchronous segment or a free slot):
-      // yield the issue slots to the walkers
+      // yield the issue slots to the walkers (!TK: ST_EMIT here is an emission queued, or one
+      // whose slot is still busy)
       if (__ballot(P.st != ST_IDLE && !(P.has(LF_WAIT) || P.has(LF_REQ) || P.has(LF_EVQ) ||
-                                        (P.st == ST_ABSORB && !P.has(LF_CELLS)))) == 0) {
+                                        (P.st == ST_ABSORB && !P.has(LF_CELLS)) || (!TK && P.st == ST_EMIT))) == 0) {
         WSDIAG(WD_PSLEEP, 1);
         __builtin_amdgcn_s_sleep(1);  // (0, 3: within noise)
         // the watchdog: an event, segment or slot that never comes (a lost enqueue) would hold
