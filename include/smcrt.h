@@ -356,6 +356,37 @@ int smcrt_voxel_scene_create(const uint8_t* labels, const smcrt_medium* media, i
                              const smcrt_grid* grid, const smcrt_detector* dets, int32_t n_dets,
                              int32_t device, smcrt_scene** out);
 
+/* ---- mesh media ------------------------------------------------------------------------------
+ * A third kind of scene: closed triangle surfaces between media, a table of media and the ambient
+ * medium; no SDF (DESIGN.md §7 "Mesh media" defines the transport). A photon flies from surface to
+ * surface by a ray cast through a bounding-volume hierarchy built at creation, and meets each
+ * interface with the triangle's own normal. The world ends at the grid.
+ *   verts[nv][3]: vertices, in the centred coordinates of sources and detectors.
+ *   tris[nt][3]: vertex indices. A triangle's normal is N = normalise((v1 - v0) x (v2 - v0)).
+ *   tri_media[nt][2]: (outside, inside), 0-based indices into media[n_media]: `outside` is the
+ *   medium on the side N points to, `inside` the medium on the other side.
+ *   media, n_media (1 .. 256): as for voxel scenes; kappa == 0 is a void. `ambient` is the medium of
+ *   a point from which a cast meets nothing. A photon's `layer` is its medium index + 1.
+ * Every argument is validated before any device call; SMCRT_ERR_INVALID_ARG names the first
+ * offender: a NULL pointer, a count out of range, a non-finite vertex, a vertex index out of
+ * range, a degenerate triangle (|e1 x e2| == 0), a medium index >= n_media, a bad medium, or a
+ * surface that is not closed and consistently oriented: every undirected edge must occur in
+ * exactly two triangles, once in each direction, and both must carry the same (outside, inside).
+ * Surfaces may be nested or disjoint. Surfaces that intersect each other are NOT detected: a
+ * photon that finds itself in another medium than the triangle it meets expects ends as a fault
+ * (status 3, SMCRT_CTR_FAULTS). nt above 2^30 gives SMCRT_ERR_UNSUPPORTED; valid arguments without
+ * a GPU give SMCRT_ERR_NO_DEVICE.
+ * The result is an ordinary smcrt_scene, served and refused exactly as a voxel scene is (above;
+ * the messages name mesh scenes). smcrt_scene_info gives n_top = n_media; smcrt_scene_classify
+ * makes a host cast from the point along (0, 0, 1): the medium is `inside` of the first triangle
+ * met if the ray leaves through it (dir . N > 0), `outside` if it enters, `ambient` without a hit;
+ * layer = medium + 1, 0 outside the grid. smcrt_kernel_times::far_steps counts the nodes of the
+ * hierarchy that the casts visited; SMCRT_CTR_GRID_UPDATES counts the casts (one per leg). */
+int smcrt_mesh_scene_create(const double* verts, int32_t nv, const int32_t* tris, const uint8_t* tri_media,
+                            int32_t nt, const smcrt_medium* media, int32_t n_media, int32_t ambient,
+                            const smcrt_grid* grid, const smcrt_detector* dets, int32_t n_dets,
+                            int32_t device, smcrt_scene** out);
+
 /* The scene's fluence grid, number of top-level SDFs and of detectors (any may be NULL). */
 int smcrt_scene_info(const smcrt_scene* scene, smcrt_grid* grid, int32_t* n_top, int32_t* n_dets);
 

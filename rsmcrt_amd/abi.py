@@ -280,4 +280,5 @@ EXPORTED_SYMBOLS = [
     "smcrt_scene_set_phasor", "smcrt_scene_read_phasor", "smcrt_scene_reset_phasor",
     "smcrt_displacement_compile", "smcrt_displacement_eval", "smcrt_displacement_describe",
     "smcrt_voxel_scene_create", "smcrt_scene_deposit_regime",
+    "smcrt_mesh_scene_create",
 ]

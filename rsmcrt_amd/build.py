@@ -40,7 +40,9 @@ UNITS = [(src, ()) for src in SOURCES] + [
     # build on 8 cores took 1 min 43 s against 1 min 47 s before (11.7 against 10.9 min of CPU
     # time): parts 0 and 1 compile a shorter ws_kernel, which pays for most of the new units.
     (KINST, (f"-DKI_F={f}", f"-DKI_G={g}", f"-DKI_P={p}") + (PLAIN_WS_FLAGS if p == 5 else ()))
-    for f in (0, 1) for g in (0, 1, 2) for p in (5, 6)]
+    for f in (0, 1) for g in (0, 1, 2) for p in (5, 6)] + [
+    # part 7: mesh_kernel (mesh.h: closed triangle surfaces; its faces are always staged in LDS)
+    (KINST, ("-DKI_F=0", f"-DKI_G={g}", "-DKI_P=7")) for g in (0, 1, 2)]
 DEPS = SOURCES + [KINST] + sorted(glob.glob(os.path.join(PKG, "csrc", "*.h"))) + [os.path.join(ROOT, "include", "smcrt.h")]
 ARCH = os.environ.get("SMCRT_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=off: no fused multiply-add, so fp64 trajectories are bit-identical to the

@@ -8,6 +8,8 @@ from __future__ import annotations
 import math
 from typing import Sequence, Tuple
 
+import numpy as np
+
 from . import abi
 from .scene import (Scene, box, capsule, cylinder, invert, model, mono, rotate_y, sphere, torus,
                     translate, egg, revolution)
@@ -195,3 +197,61 @@ def skin_layers():
         box((0.1, 0.1, 0.1), mono(0.0, 0.0, 0.0, 1.0), 4),
     ]
     return Scene(sdfs)
+
+
+# ---- closed triangle surfaces for scene.MeshScene: (verts (nv, 3) float64, tris (nt, 3) int32), normals outward ----
+def box_mesh(lo, hi):
+    """The axis-aligned box [lo, hi] as 8 vertices and 12 triangles."""
+    (x0, y0, z0), (x1, y1, z1) = lo, hi
+    v = np.array([[x, y, z] for z in (z0, z1) for y in (y0, y1) for x in (x0, x1)], dtype=np.float64)
+    t = np.array([[0, 2, 3], [0, 3, 1],   # z = z0 (normal -z)
+                  [4, 5, 7], [4, 7, 6],   # z = z1 (+z)
+                  [0, 1, 5], [0, 5, 4],   # y = y0 (-y)
+                  [2, 6, 7], [2, 7, 3],   # y = y1 (+y)
+                  [0, 4, 6], [0, 6, 2],   # x = x0 (-x)
+                  [1, 3, 7], [1, 7, 5]],  # x = x1 (+x)
+                 dtype=np.int32)
+    return v, t
+
+
+def icosphere(level, radius=1.0, centre=(0.0, 0.0, 0.0)):
+    """An icosahedron subdivided `level` times (20 * 4^level triangles), vertices on the sphere."""
+    g = (1.0 + math.sqrt(5.0)) / 2.0
+    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g),
+         (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    v = [tuple(np.array(p, dtype=np.float64) / math.sqrt(1.0 + g * g)) for p in v]
+    t = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+         (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10),
+         (8, 6, 7), (9, 8, 1)]
+    for _ in range(int(level)):
+        mid, nt = {}, []
+
+        def midpoint(a, b):
+            key = (a, b) if a < b else (b, a)
+            if key not in mid:
+                m = (np.array(v[a]) + np.array(v[b])) / 2.0
+                v.append(tuple(m / np.sqrt(np.dot(m, m))))
+                mid[key] = len(v) - 1
+            return mid[key]
+
+        for a, b, c in t:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            nt += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        t = nt
+    return np.array(v, dtype=np.float64) * float(radius) + np.array(centre, dtype=np.float64), np.array(t, dtype=np.int32)
+
+
+def torus_mesh(R, r, nu=32, nv=16):
+    """The torus of major radius R and tube radius r about the z axis: nu steps around the axis, nv
+    around the tube, 2 nu nv triangles."""
+    u = np.arange(nu) * (2.0 * math.pi / nu)
+    w = np.arange(nv) * (2.0 * math.pi / nv)
+    uu, ww = np.meshgrid(u, w, indexing="ij")
+    v = np.stack([(R + r * np.cos(ww)) * np.cos(uu), (R + r * np.cos(ww)) * np.sin(uu), r * np.sin(ww)], axis=-1).reshape(-1, 3)
+    t = []
+    for i in range(nu):
+        for j in range(nv):
+            a, b = i * nv + j, ((i + 1) % nu) * nv + j
+            c, d = ((i + 1) % nu) * nv + (j + 1) % nv, i * nv + (j + 1) % nv
+            t += [(a, b, c), (a, c, d)]
+    return np.ascontiguousarray(v, dtype=np.float64), np.array(t, dtype=np.int32)

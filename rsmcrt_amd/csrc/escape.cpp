@@ -485,7 +485,7 @@ int smcrt_escape_run(smcrt_scene* scene, const smcrt_source* src, const smcrt_es
   int st = make_sym(cfg, &S);
   if (st) return st;
   if (!scene || !run || !io) return set_error(SMCRT_ERR_INVALID_ARG, "NULL argument");
-  if (const int vst = smcrt::scene_refuse_voxel(scene, "smcrt_escape_run")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(scene, "smcrt_escape_run")) return vst;
   if (run->flags & SMCRT_FLAG_TRACK_PATHS)
     return set_error(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
   if (run->flags & SMCRT_FLAG_PHASOR)

@@ -25,7 +25,7 @@ extern "C" {
 int smcrt_inverse_run(smcrt_scene* scene, const smcrt_source* src, const smcrt_inverse_config* cfg,
                       const smcrt_run_config* run, const double* targets, double* steps, smcrt_tallies* io) {
   if (!scene || !src || !cfg || !run || !steps) return set_error(SMCRT_ERR_INVALID_ARG, "NULL argument");
-  if (const int vst = smcrt::scene_refuse_voxel(scene, "smcrt_inverse_run")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(scene, "smcrt_inverse_run")) return vst;
   if (cfg->max_steps < 1) return set_error(SMCRT_ERR_INVALID_ARG, "maxNumSteps must be >= 1");
   if (run->flags & SMCRT_FLAG_TRACK_PATHS)
     return set_error(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");

@@ -5,7 +5,8 @@
 // and the XF ws_kernel of test_kernel runs, TK = true in ws.h; part 2, F = 0 only:
 // transport_kernel's HIST instantiations, the photon path recorder of paths.h; part 3, F = 0
 // only: its PHAS instantiations, the phasor tally of phasor.h; part 4, F = 0 only: voxel_kernel,
-// the label-volume transport of voxel.h), so
+// the label-volume transport of voxel.h; part 7, F = 0 only: mesh_kernel, the triangle-surface
+// transport of mesh.h), so
 // the instantiations of transport_kernel and ws_kernel (kernels.h, ws.h) build in parallel
 // instead of in one translation unit. Each object exports these getters; hipLaunchKernel and
 // the occupancy queries take the host stubs they return.
@@ -57,6 +58,13 @@ SMCRT_KINST_VOXEL_DECL(0)
 SMCRT_KINST_VOXEL_DECL(1)
 SMCRT_KINST_VOXEL_DECL(2)
 #undef SMCRT_KINST_VOXEL_DECL
+#define SMCRT_KINST_MESH_DECL(G)               \
+  const void* kinst_mesh_0_##G(int xsrc);      \
+  void kinst_diagm_0_##G(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6);
+SMCRT_KINST_MESH_DECL(0)
+SMCRT_KINST_MESH_DECL(1)
+SMCRT_KINST_MESH_DECL(2)
+#undef SMCRT_KINST_MESH_DECL
 
 // transport_kernel<lds_faces, gm, xsrc, coop, hist, phas>; the general emitter with the COOP
 // machinery (xsrc && coop), the path recorder (hist, paths.h) and the phasor tally (phas,
@@ -83,6 +91,11 @@ inline const void* transport_kernel_ptr(bool lds_faces, int gm, bool xsrc, bool 
 inline const void* voxel_kernel_ptr(int gm, bool xsrc) {
   const int x = xsrc ? 1 : 0;
   return gm == 0 ? kinst_voxel_0_0(x) : gm == 1 ? kinst_voxel_0_1(x) : kinst_voxel_0_2(x);
+}
+// mesh_kernel<gm, xsrc> (mesh.h)
+inline const void* mesh_kernel_ptr(int gm, bool xsrc) {
+  const int x = xsrc ? 1 : 0;
+  return gm == 0 ? kinst_mesh_0_0(x) : gm == 1 ? kinst_mesh_0_1(x) : kinst_mesh_0_2(x);
 }
 // ws_kernel<lds_faces, gm, xf, slots, iv, tk> (xf: the Fresnel/detector program points; slots 2 or
 // 3; iv: the in-voxel segments' code, always in the plain instantiation; tk: a run with
@@ -114,6 +127,7 @@ inline void kinst_diag_gather(unsigned long long* d72, unsigned long long* t9, u
   kinst_diagh_0_0(d72, t9, c6); kinst_diagh_0_1(d72, t9, c6); kinst_diagh_0_2(d72, t9, c6);
   kinst_diagf_0_0(d72, t9, c6); kinst_diagf_0_1(d72, t9, c6); kinst_diagf_0_2(d72, t9, c6);
   kinst_diagv_0_0(d72, t9, c6); kinst_diagv_0_1(d72, t9, c6); kinst_diagv_0_2(d72, t9, c6);
+  kinst_diagm_0_0(d72, t9, c6); kinst_diagm_0_1(d72, t9, c6); kinst_diagm_0_2(d72, t9, c6);
 }
 
 }  // namespace smcrt

@@ -278,7 +278,7 @@ int smcrt_reduce_device_tallies(smcrt_scene* scene, smcrt_comm* cm, smcrt_device
                                 void* stream) {
   g_last_error.clear();
   if (!scene || !cm || !dev) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
-  if (const int vst = smcrt::scene_refuse_voxel(scene, "smcrt_reduce_device_tallies")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(scene, "smcrt_reduce_device_tallies")) return vst;
   if (root >= cm->n_ranks) return fail(SMCRT_ERR_INVALID_ARG, "root out of range");
   if (smcrt::scene_device(scene) != cm->device) return fail(SMCRT_ERR_INVALID_ARG, "scene and comm are on different devices");
   const Rccl& R = rccl();

@@ -12,9 +12,10 @@ int scene_node_optprops(const smcrt_scene* s, int32_t top, double out[4]);
 // with its own flags), and the flags themselves
 int scene_set_node_props(smcrt_scene* s, int32_t top, double mus, double mua, double hgg, double n, int32_t flags);
 int scene_node_flags(const smcrt_scene* s, int32_t top, int32_t* flags);
-// SMCRT_ERR_UNSUPPORTED with a message naming `what` if the scene is a voxel scene
-// (smcrt_voxel_scene_create), else SMCRT_OK: the entry points that need SDFs open with it
-int scene_refuse_voxel(const smcrt_scene* s, const char* what);
+// SMCRT_ERR_UNSUPPORTED with a message naming `what` and the scene's kind if the scene is a voxel
+// scene (smcrt_voxel_scene_create) or a mesh scene (smcrt_mesh_scene_create), else SMCRT_OK: the
+// entry points that need SDFs open with it
+int scene_needs_sdf(const smcrt_scene* s, const char* what);
 // doubles of detector data detector d owns
 int scene_det_size(const smcrt_scene* s, int32_t d, int64_t* n);
 // the HIP device and the scene's own launch stream (a hipStream_t), for the multi-GPU driver

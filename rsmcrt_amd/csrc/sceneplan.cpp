@@ -289,6 +289,34 @@ void plan_deposit(const smcrt_grid* grid, const Knobs& knobs, ScenePlan& p) {
   p.hist_tiles = (!p.bucketed && knobs.fused_hist && p.n_tiles > 0 && p.n_tiles <= MAX_FUSED_HIST_TILES) ? p.n_tiles : 0;
 }
 
+// the media checks of both label volumes and meshes; `kind` opens the message
+int check_media(const char* kind, const smcrt_medium* media, int32_t n_media) {
+  const std::string k = std::string(kind) + ": medium ";
+  for (int32_t i = 0; i < n_media; ++i) {
+    const smcrt_medium& m = media[i];
+    if (!(m.mus >= 0.0) || !(m.mua >= 0.0) || !std::isfinite(m.mus) || !std::isfinite(m.mua))
+      return fail(SMCRT_ERR_INVALID_ARG, k + std::to_string(i) + ": mus and mua must be finite and >= 0");
+    if (!(std::fabs(m.hgg) <= 1.0)) return fail(SMCRT_ERR_INVALID_ARG, k + std::to_string(i) + ": |hgg| must be <= 1");
+    if (!(m.n > 0.0) || !std::isfinite(m.n))
+      return fail(SMCRT_ERR_INVALID_ARG, k + std::to_string(i) + ": n must be finite and > 0");
+  }
+  return SMCRT_OK;
+}
+
+// a placeholder node per medium carries its mus, mua, hgg, n (voxel and mesh scenes)
+void plan_media(const smcrt_medium* media, int32_t n_media, ScenePlan& p) {
+  p.n_nodes = p.n_top = n_media;
+  for (int32_t i = 0; i < n_media; ++i) {
+    smcrt_sdf_node nd;
+    std::memset(&nd, 0, sizeof nd);
+    nd.layer = i + 1;
+    nd.mus = media[i].mus; nd.mua = media[i].mua; nd.hgg = media[i].hgg; nd.n = media[i].n;
+    p.h_nodes.push_back(nd);
+    p.h_top.push_back(i);
+    p.h_props.push_back(make_props(nd));
+  }
+}
+
 }  // namespace
 
 int plan_scene(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top, int32_t n_top, const smcrt_grid* grid,
@@ -364,15 +392,7 @@ int plan_voxel_scene(const uint8_t* labels, const smcrt_medium* media, int32_t n
     return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: grid dimensions must be positive and finite");
   const uint64_t nv = (uint64_t)grid->nx * (uint64_t)grid->ny * (uint64_t)grid->nz;
   if (nv >= (1ull << 32)) return fail(SMCRT_ERR_UNSUPPORTED, "grids of 2^32 or more voxels are not supported");
-  for (int32_t i = 0; i < n_media; ++i) {
-    const smcrt_medium& m = media[i];
-    if (!(m.mus >= 0.0) || !(m.mua >= 0.0) || !std::isfinite(m.mus) || !std::isfinite(m.mua))
-      return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: medium " + std::to_string(i) + ": mus and mua must be finite and >= 0");
-    if (!(std::fabs(m.hgg) <= 1.0))
-      return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: medium " + std::to_string(i) + ": |hgg| must be <= 1");
-    if (!(m.n > 0.0) || !std::isfinite(m.n))
-      return fail(SMCRT_ERR_INVALID_ARG, "voxel scene: medium " + std::to_string(i) + ": n must be finite and > 0");
-  }
+  if (const int mst = check_media("voxel scene", media, n_media)) return mst;
   for (uint64_t v = 0; v < nv; ++v)
     if (labels[v] >= n_media) {
       const uint64_t i = v % (uint64_t)grid->nx, j = (v / (uint64_t)grid->nx) % (uint64_t)grid->ny,
@@ -387,19 +407,10 @@ int plan_voxel_scene(const uint8_t* labels, const smcrt_medium* media, int32_t n
       return fail(SMCRT_ERR_INVALID_ARG, "bad detector " + std::to_string(i));
   ScenePlan& p = *out;
   p.voxel = true;
-  p.n_nodes = p.n_top = n_media;
   p.n_dets = n_dets;
   p.grid = *grid;
   p.labels.assign(labels, labels + nv);
-  for (int32_t i = 0; i < n_media; ++i) {  // a placeholder node per medium carries its mus, mua, hgg, n
-    smcrt_sdf_node nd;
-    std::memset(&nd, 0, sizeof nd);
-    nd.layer = i + 1;
-    nd.mus = media[i].mus; nd.mua = media[i].mua; nd.hgg = media[i].hgg; nd.n = media[i].n;
-    p.h_nodes.push_back(nd);
-    p.h_top.push_back(i);
-    p.h_props.push_back(make_props(nd));
-  }
+  plan_media(media, n_media, p);
   plan_detectors(dets, n_dets, p);
   plan_faces(grid, p);
   plan_grid_mode(grid, p);
@@ -421,6 +432,201 @@ int32_t host_vox_of(double p, int32_t n, double max) {  // get_voxel_cart, grid.
   const double f = std::floor(((double)n * (p + max)) / (2.0 * max));
   if (!(f >= 0.0 && f < (double)n)) return -1;
   return (int32_t)f + 1;
+}
+
+// ---- mesh media ----------------------------------------------------------------------------
+namespace {
+
+struct MeshEdge {
+  int32_t a, b;  // a < b
+  int32_t tri;
+  bool fwd;      // the triangle runs it a -> b
+};
+
+// Every undirected edge in exactly two triangles, once in each direction, both with the same pair
+// of media. Names the offending edge with the smallest triangle index.
+int check_closed(const int32_t* tris, const uint8_t* tri_media, int32_t nt) {
+  std::vector<MeshEdge> edges;
+  edges.reserve((size_t)3 * nt);
+  for (int32_t t = 0; t < nt; ++t)
+    for (int k = 0; k < 3; ++k) {
+      const int32_t a = tris[3 * t + k], b = tris[3 * t + (k + 1) % 3];
+      edges.push_back(a < b ? MeshEdge{a, b, t, true} : MeshEdge{b, a, t, false});
+    }
+  std::sort(edges.begin(), edges.end(), [](const MeshEdge& x, const MeshEdge& y) {
+    return x.a != y.a ? x.a < y.a : (x.b != y.b ? x.b < y.b : x.tri < y.tri);
+  });
+  int32_t worst = -1;
+  std::string msg;
+  for (size_t i = 0; i < edges.size();) {
+    size_t j = i;
+    while (j < edges.size() && edges[j].a == edges[i].a && edges[j].b == edges[i].b) ++j;
+    const MeshEdge& e = edges[i];  // (the group's smallest triangle index)
+    std::string why;
+    if (j - i != 2) {
+      why = "occurs in " + std::to_string(j - i) + " triangle(s), not in exactly two: the surface is not closed";
+    } else {
+      const MeshEdge& f = edges[i + 1];
+      if (e.fwd == f.fwd)
+        why = "runs the same way in triangles " + std::to_string(e.tri) + " and " + std::to_string(f.tri) +
+              ": the surface is not consistently oriented";
+      else if (tri_media[2 * e.tri] != tri_media[2 * f.tri] || tri_media[2 * e.tri + 1] != tri_media[2 * f.tri + 1])
+        why = "joins triangles " + std::to_string(e.tri) + " and " + std::to_string(f.tri) +
+              ", which carry different (outside, inside) media";
+    }
+    if (!why.empty() && (worst < 0 || e.tri < worst)) {
+      worst = e.tri;
+      msg = "mesh scene: triangle " + std::to_string(e.tri) + ": edge (" + std::to_string(e.a) + ", " + std::to_string(e.b) +
+            ") " + why;
+    }
+    i = j;
+  }
+  return worst < 0 ? SMCRT_OK : fail(SMCRT_ERR_INVALID_ARG, msg);
+}
+
+// The hierarchy over tris[b, e) (already in p.mesh_tris), depth-first; returns nothing, appends nodes.
+void build_bvh(ScenePlan& p, std::vector<double>& cen, int32_t b, int32_t e, double pad) {
+  const size_t self = p.mesh_nodes.size();
+  p.mesh_nodes.push_back(MeshNode{});
+  double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+  double clo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, chi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+  for (int32_t k = b; k < e; ++k) {
+    const MeshTri& T = p.mesh_tris[k];
+    for (int a = 0; a < 3; ++a) {
+      // (the corners as v0 + e rounds them; the pad covers the rounding many times over)
+      const double c[3] = {T.v0[a], T.v0[a] + T.e1[a], T.v0[a] + T.e2[a]};
+      for (double x : c) { lo[a] = std::min(lo[a], x); hi[a] = std::max(hi[a], x); }
+      clo[a] = std::min(clo[a], cen[3 * (size_t)T.id + a]);
+      chi[a] = std::max(chi[a], cen[3 * (size_t)T.id + a]);
+    }
+  }
+  {
+    MeshNode& nd = p.mesh_nodes[self];
+    for (int a = 0; a < 3; ++a) { nd.lo[a] = lo[a] - pad; nd.hi[a] = hi[a] + pad; }
+    nd.first = b;
+    nd.count = e - b <= MESH_LEAF_TRIS ? e - b : 0;
+    nd.reserved = 0;
+  }
+  if (e - b > MESH_LEAF_TRIS) {
+    int ax = 0;
+    if (chi[1] - clo[1] > chi[ax] - clo[ax]) ax = 1;
+    if (chi[2] - clo[2] > chi[ax] - clo[ax]) ax = 2;
+    std::sort(p.mesh_tris.begin() + b, p.mesh_tris.begin() + e, [&](const MeshTri& x, const MeshTri& y) {
+      const double cx = cen[3 * (size_t)x.id + ax], cy = cen[3 * (size_t)y.id + ax];
+      return cx != cy ? cx < cy : x.id < y.id;
+    });
+    const int32_t mid = b + (e - b) / 2;
+    build_bvh(p, cen, b, mid, pad);
+    build_bvh(p, cen, mid, e, pad);
+  }
+  p.mesh_nodes[self].skip = (int32_t)p.mesh_nodes.size();  // the node after this subtree
+}
+
+}  // namespace
+
+int plan_mesh_scene(const double* verts, int32_t nv, const int32_t* tris, const uint8_t* tri_media, int32_t nt,
+                    const smcrt_medium* media, int32_t n_media, int32_t ambient, const smcrt_grid* grid,
+                    const smcrt_detector* dets, int32_t n_dets, const Knobs& knobs, ScenePlan* out) {
+  if (!verts || !tris || !tri_media || !media || !grid || n_dets < 0 || (n_dets > 0 && !dets))
+    return fail(SMCRT_ERR_INVALID_ARG, "mesh scene: NULL argument");
+  if (n_media < 1 || n_media > 256)
+    return fail(SMCRT_ERR_INVALID_ARG, "mesh scene: n_media = " + std::to_string(n_media) + " is outside 1 .. 256");
+  if (ambient < 0 || ambient >= n_media)
+    return fail(SMCRT_ERR_INVALID_ARG, "mesh scene: ambient = " + std::to_string(ambient) + " is not below n_media = " +
+                                           std::to_string(n_media));
+  if (nv < 4 || nt < 4)
+    return fail(SMCRT_ERR_INVALID_ARG, "mesh scene: nv = " + std::to_string(nv) + ", nt = " + std::to_string(nt) +
+                                           ": a closed surface has at least 4 vertices and 4 triangles");
+  if (nt > MESH_MAX_TRIS)
+    return fail(SMCRT_ERR_UNSUPPORTED, "mesh scene: nt = " + std::to_string(nt) + " is above the " +
+                                           std::to_string(MESH_MAX_TRIS) + " triangles that 32-bit node links allow");
+  if (grid->nx < 1 || grid->ny < 1 || grid->nz < 1 || !(grid->xmax > 0) || !(grid->ymax > 0) || !(grid->zmax > 0) ||
+      !std::isfinite(grid->xmax) || !std::isfinite(grid->ymax) || !std::isfinite(grid->zmax))
+    return fail(SMCRT_ERR_INVALID_ARG, "mesh scene: grid dimensions must be positive and finite");
+  if ((uint64_t)grid->nx * (uint64_t)grid->ny * (uint64_t)grid->nz >= (1ull << 32))
+    return fail(SMCRT_ERR_UNSUPPORTED, "grids of 2^32 or more voxels are not supported");
+  if (const int mst = check_media("mesh scene", media, n_media)) return mst;
+  double scale = std::max(grid->xmax, std::max(grid->ymax, grid->zmax));
+  for (int64_t i = 0; i < (int64_t)3 * nv; ++i) {
+    if (!std::isfinite(verts[i]))
+      return fail(SMCRT_ERR_INVALID_ARG, "mesh scene: vertex " + std::to_string(i / 3) + " is not finite");
+    scale = std::max(scale, std::fabs(verts[i]));
+  }
+  for (int32_t t = 0; t < nt; ++t)
+    for (int k = 0; k < 3; ++k)
+      if (tris[3 * t + k] < 0 || tris[3 * t + k] >= nv)
+        return fail(SMCRT_ERR_INVALID_ARG, "mesh scene: triangle " + std::to_string(t) + ": vertex index " +
+                                               std::to_string(tris[3 * t + k]) + " is outside 0 .. nv - 1 = " +
+                                               std::to_string(nv - 1));
+  for (int32_t t = 0; t < nt; ++t)
+    for (int k = 0; k < 2; ++k)
+      if (tri_media[2 * t + k] >= n_media)
+        return fail(SMCRT_ERR_INVALID_ARG, "mesh scene: triangle " + std::to_string(t) + ": medium index " +
+                                               std::to_string((int)tri_media[2 * t + k]) + " is not below n_media = " +
+                                               std::to_string(n_media));
+  for (int32_t i = 0; i < n_dets; ++i)
+    if (dets[i].kind < SMCRT_DET_CIRCLE || dets[i].kind > SMCRT_DET_FIBRE || dets[i].nbins < 1)
+      return fail(SMCRT_ERR_INVALID_ARG, "bad detector " + std::to_string(i));
+  ScenePlan& p = *out;
+  p.mesh_tris.resize(nt);
+  p.mesh_faces.resize(nt);
+  std::vector<double> cen((size_t)3 * nt);
+  for (int32_t t = 0; t < nt; ++t) {
+    const double *v0 = verts + 3 * (size_t)tris[3 * t], *v1 = verts + 3 * (size_t)tris[3 * t + 1],
+                 *v2 = verts + 3 * (size_t)tris[3 * t + 2];
+    MeshTri& T = p.mesh_tris[t];
+    for (int a = 0; a < 3; ++a) {
+      T.v0[a] = v0[a];
+      T.e1[a] = v1[a] - v0[a];
+      T.e2[a] = v2[a] - v0[a];
+      cen[3 * (size_t)t + a] = (v0[a] + v1[a] + v2[a]) / 3.0;
+    }
+    T.id = t;
+    T.reserved = 0;
+    // N = normalise(e1 x e2), with sqrt and / (exact under IEEE)
+    const double cx = T.e1[1] * T.e2[2] - T.e1[2] * T.e2[1], cy = T.e1[2] * T.e2[0] - T.e1[0] * T.e2[2],
+                 cz = T.e1[0] * T.e2[1] - T.e1[1] * T.e2[0];
+    const double len = std::sqrt(cx * cx + cy * cy + cz * cz);
+    if (len == 0.0 || !std::isfinite(len))
+      return fail(SMCRT_ERR_INVALID_ARG, "mesh scene: triangle " + std::to_string(t) + " is degenerate (|e1 x e2| == 0)");
+    MeshFace& F = p.mesh_faces[t];
+    F.N[0] = cx / len; F.N[1] = cy / len; F.N[2] = cz / len;
+    F.outside = tri_media[2 * t];
+    F.inside = tri_media[2 * t + 1];
+  }
+  if (const int cst = check_closed(tris, tri_media, nt)) return cst;
+  p.mesh = true;
+  p.mesh_ambient = ambient;
+  p.n_dets = n_dets;
+  p.grid = *grid;
+  p.mesh_nodes.reserve((size_t)nt);
+  // boxes are padded by 2^-20 of the scene's size: the exact test's hit point lies in the unpadded
+  // box up to the rounding of t, u, v, which the pad exceeds unless |det| is below ~1e-9 of its scale
+  build_bvh(p, cen, 0, nt, scale * 0x1.0p-20);
+  plan_media(media, n_media, p);
+  plan_detectors(dets, n_dets, p);
+  plan_faces(grid, p);
+  plan_grid_mode(grid, p);
+  plan_deposit(grid, knobs, p);
+  // mesh_kernel stages the media and the faces in LDS whatever their size
+  p.face_bytes = p.faces.size() * sizeof(double) + sizeof(TopProps) * (size_t)n_media;
+  p.lds_faces = true;
+  if (p.face_bytes > MAX_FACE_BYTES)
+    return fail(SMCRT_ERR_UNSUPPORTED, "mesh scene: nx + ny + nz is too large for the faces to be staged in LDS");
+  for (int32_t i = 1; i < n_media; ++i) p.fresnel = p.fresnel || p.h_props[i].n != p.h_props[0].n;
+  p.lean_mode = 0;
+  p.lean_candidate = false;  // ws_kernel has no cast
+  p.fold_prio = knobs.fold_prio;
+  p.verbose = knobs.verbose;
+  return SMCRT_OK;
+}
+
+int32_t mesh_medium_at(const ScenePlan& p, const double pt[3]) {
+  const double d[3] = {0.0, 0.0, 1.0};
+  const MeshHit h = mesh_cast(p.mesh_nodes.data(), (uint32_t)p.mesh_nodes.size(), p.mesh_tris.data(), pt, d, MESH_NONE);
+  if (h.tri == MESH_NONE) return p.mesh_ambient;
+  const MeshFace& F = p.mesh_faces[h.tri];
+  return (int32_t)((d[0] * F.N[0] + d[1] * F.N[1] + d[2] * F.N[2]) > 0.0 ? F.inside : F.outside);
 }
 
 }  // namespace smcrt

@@ -149,6 +149,14 @@ struct ScenePlan {
   // kinds of scene
   bool voxel = false;
   std::vector<uint8_t> labels;
+  // mesh media (plan_mesh_scene): the threaded hierarchy, the triangles in its order and the faces
+  // by the caller's triangle index (meshcast.h); h_props, h_nodes and h_top hold the media as in a
+  // voxel scene
+  bool mesh = false;
+  int32_t mesh_ambient = 0;
+  std::vector<MeshNode> mesh_nodes;
+  std::vector<MeshTri> mesh_tris;
+  std::vector<MeshFace> mesh_faces;
 };
 
 // Validate the scene and decide everything about it that needs no device. Returns SMCRT_OK,
@@ -170,6 +178,21 @@ int32_t host_vox_of(double p, int32_t n, double max);
 inline size_t voxel_lds(const ScenePlan& p, uint32_t dep_words) {
   return p.face_bytes + (size_t)dep_words * sizeof(uint32_t);
 }
+
+// A mesh scene (smcrt_mesh_scene_create): validates (finite vertices, indices in range, no
+// degenerate triangle, media, every surface closed and consistently oriented with one pair of
+// media along each edge), builds the hierarchy (median split of the centroids on the longest axis,
+// leaves of at most MESH_LEAF_TRIS triangles, depth-first order, padded boxes) and fills what a
+// launch of mesh_kernel needs, as plan_voxel_scene does. Surfaces that intersect each other are
+// not detected. Same return convention as plan_scene.
+int plan_mesh_scene(const double* verts, int32_t nv, const int32_t* tris, const uint8_t* tri_media, int32_t nt,
+                    const smcrt_medium* media, int32_t n_media, int32_t ambient, const smcrt_grid* grid,
+                    const smcrt_detector* dets, int32_t n_dets, const Knobs& knobs, ScenePlan* out);
+// The medium (0-based) of centred point p of a mesh plan: a host cast along (0, 0, 1) and the
+// emission rule (inside(tri) if dir . N > 0 at the hit, outside(tri) if not, ambient without a hit)
+int32_t mesh_medium_at(const ScenePlan& p, const double pt[3]);
+// Dynamic LDS of mesh_kernel (mesh.h): voxel_kernel's layout
+inline size_t mesh_lds(const ScenePlan& p, uint32_t dep_words) { return voxel_lds(p, dep_words); }
 
 // ---- pure rules of the launch path ----
 // the lean path's dynamic LDS (ws_kernel): staged props + faces, then the block's bucket words

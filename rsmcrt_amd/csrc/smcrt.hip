@@ -97,6 +97,9 @@ struct smcrt_scene : ScenePlan {
   DevBuf<unsigned char> d_cull_data;
   DevBuf<TopProps> d_props;
   DevBuf<uint8_t> d_labels;  // a voxel scene's labels (voxel.h), or NULL
+  DevBuf<MeshNode> d_mesh_nodes;  // a mesh scene's hierarchy, triangles and faces (mesh.h), or NULL
+  DevBuf<MeshTri> d_mesh_tris;
+  DevBuf<MeshFace> d_mesh_faces;
   DevBuf<double> d_faces;
   DevBuf<smcrt_detector> d_dets;
   DevBuf<int64_t> d_det_off;
@@ -394,7 +397,9 @@ static void size_grids(smcrt_scene* s) {
                  (int)s->lean_ok, s->ws_slots, s->grid_blocks_ws / std::max(1, cus), kinst_ws_shared_bytes(s->ws_slots), lean_lds(*s),
                  s->grid_blocks);
   for (int x = 0; x < 2; ++x) {
-    hipError_t oe = s->voxel ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, voxel_kernel_ptr(s->grid_mode, x == 1),
+    hipError_t oe = s->mesh  ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mesh_kernel_ptr(s->grid_mode, x == 1),
+                                                                            256, mesh_lds(*s, dep_words(*s)))
+                    : s->voxel ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, voxel_kernel_ptr(s->grid_mode, x == 1),
                                                                             256, voxel_lds(*s, dep_words(*s)))
                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, transport_fn(s, x == 1), 256,
                                                                             transport_lds(*s, dep_words(*s), x == 1));
@@ -444,6 +449,33 @@ int smcrt_voxel_scene_create(const uint8_t* labels, const smcrt_medium* media, i
   s->device = device;
   if (hipSetDevice(device) != hipSuccess) return fail(SMCRT_ERR_HIP, "hipSetDevice failed");
   if ((st = upload_plan(s.get())) || (st = upload(s->d_labels, s->labels.data(), s->labels.size(), "label upload")) ||
+      (s->n_tiles && (st = create_fold_state(s.get()))))
+    return st;
+  size_grids(s.get());
+  *out = s.release();
+  return SMCRT_OK;
+}
+
+int smcrt_mesh_scene_create(const double* verts, int32_t nv, const int32_t* tris, const uint8_t* tri_media, int32_t nt,
+                            const smcrt_medium* media, int32_t n_media, int32_t ambient, const smcrt_grid* grid,
+                            const smcrt_detector* dets, int32_t n_dets, int32_t device, smcrt_scene** out) {
+  g_last_error.clear();
+  if (!out) return fail(SMCRT_ERR_INVALID_ARG, "out is NULL");
+  *out = nullptr;
+  ScenePlan plan;
+  int st = plan_mesh_scene(verts, nv, tris, tri_media, nt, media, n_media, ambient, grid, dets, n_dets, read_knobs(), &plan);
+  if (st) return st;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMCRT_ERR_NO_DEVICE, "no HIP device");
+  if (device < 0 || device >= ndev) return fail(SMCRT_ERR_INVALID_ARG, "device ordinal out of range");
+  std::unique_ptr<smcrt_scene, void (*)(smcrt_scene*)> s(new smcrt_scene(), smcrt_scene_destroy);
+  static_cast<ScenePlan&>(*s) = std::move(plan);
+  s->device = device;
+  if (hipSetDevice(device) != hipSuccess) return fail(SMCRT_ERR_HIP, "hipSetDevice failed");
+  if ((st = upload_plan(s.get())) ||
+      (st = upload(s->d_mesh_nodes, s->mesh_nodes.data(), s->mesh_nodes.size(), "mesh node upload")) ||
+      (st = upload(s->d_mesh_tris, s->mesh_tris.data(), s->mesh_tris.size(), "mesh triangle upload")) ||
+      (st = upload(s->d_mesh_faces, s->mesh_faces.data(), s->mesh_faces.size(), "mesh face upload")) ||
       (s->n_tiles && (st = create_fold_state(s.get()))))
     return st;
   size_grids(s.get());
@@ -502,18 +534,19 @@ int smcrt::scene_node_flags(const smcrt_scene* s, int32_t i, int32_t* flags) {
   return SMCRT_OK;
 }
 
-int smcrt::scene_refuse_voxel(const smcrt_scene* s, const char* what) {
-  if (!s || !s->voxel) return SMCRT_OK;
-  return fail(SMCRT_ERR_UNSUPPORTED, std::string(what) + " is not supported on voxel scenes (smcrt_voxel_scene_create)");
+int smcrt::scene_needs_sdf(const smcrt_scene* s, const char* what) {
+  if (!s || !(s->voxel || s->mesh)) return SMCRT_OK;
+  return fail(SMCRT_ERR_UNSUPPORTED, std::string(what) + (s->voxel ? " is not supported on voxel scenes (smcrt_voxel_scene_create)"
+                                                                  : " is not supported on mesh scenes (smcrt_mesh_scene_create)"));
 }
 
-// The run flags a voxel scene has no code for (voxel.h).
-static int voxel_flags_ok(const smcrt_scene* s, uint32_t flags) {
-  if (!s->voxel) return SMCRT_OK;
-  if (flags & SMCRT_FLAG_TEST_KERNEL) return smcrt::scene_refuse_voxel(s, "SMCRT_FLAG_TEST_KERNEL");
-  if (flags & SMCRT_FLAG_END_EARLY) return smcrt::scene_refuse_voxel(s, "SMCRT_FLAG_END_EARLY");
-  if (flags & SMCRT_FLAG_TRACK_PATHS) return smcrt::scene_refuse_voxel(s, "SMCRT_FLAG_TRACK_PATHS");
-  if (flags & SMCRT_FLAG_PHASOR) return smcrt::scene_refuse_voxel(s, "SMCRT_FLAG_PHASOR");
+// The run flags a voxel or a mesh scene has no code for (voxel.h, mesh.h).
+static int sdfless_flags_ok(const smcrt_scene* s, uint32_t flags) {
+  if (!s->voxel && !s->mesh) return SMCRT_OK;
+  if (flags & SMCRT_FLAG_TEST_KERNEL) return smcrt::scene_needs_sdf(s, "SMCRT_FLAG_TEST_KERNEL");
+  if (flags & SMCRT_FLAG_END_EARLY) return smcrt::scene_needs_sdf(s, "SMCRT_FLAG_END_EARLY");
+  if (flags & SMCRT_FLAG_TRACK_PATHS) return smcrt::scene_needs_sdf(s, "SMCRT_FLAG_TRACK_PATHS");
+  if (flags & SMCRT_FLAG_PHASOR) return smcrt::scene_needs_sdf(s, "SMCRT_FLAG_PHASOR");
   return SMCRT_OK;
 }
 
@@ -675,12 +708,13 @@ static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xs
       std::max<uint64_t>(1, lean ? ws_needed : blocks_needed));
   const smcrt_sdf_node* a_nodes = K.nodes;
   const ProgOp* a_prog = K.prog;
-  if (s->voxel) {  // voxel_kernel (voxel.h): transport_kernel's arguments
+  if (s->voxel || s->mesh) {  // voxel_kernel (voxel.h), mesh_kernel (mesh.h): transport_kernel's arguments
     const smcrt_detector* a_dets = K.dets;
     const int64_t* a_off = K.det_off;
     void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&a_dets, (void*)&a_off, (void*)&C};
-    HIPCHK(hipLaunchKernel(voxel_kernel_ptr(s->grid_mode, xsrc), dim3(blocks), dim3(256), args,
-                           voxel_lds(*s, dep_words(*s)), stream));
+    HIPCHK(hipLaunchKernel(s->mesh ? mesh_kernel_ptr(s->grid_mode, xsrc) : voxel_kernel_ptr(s->grid_mode, xsrc),
+                           dim3(blocks), dim3(256), args,
+                           s->mesh ? mesh_lds(*s, dep_words(*s)) : voxel_lds(*s, dep_words(*s)), stream));
   } else if (lean) {
     ++s->lean_launches;
     void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&C};
@@ -891,6 +925,11 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.vox_labels = s->d_labels;
   Ch.vox_n_media = s->voxel ? (uint32_t)s->n_top : 0u;
   Ch.vox_reserved = 0;
+  Ch.mesh_nodes = s->d_mesh_nodes;
+  Ch.mesh_tris = s->d_mesh_tris;
+  Ch.mesh_faces = s->d_mesh_faces;
+  Ch.mesh_n_nodes = (uint32_t)s->mesh_nodes.size();
+  Ch.mesh_ambient = (uint32_t)s->mesh_ambient;
 #ifdef SMCRT_DIAG
   Ch.done_time = nullptr;
   Ch.done_base = cfg->first_photon;
@@ -1036,7 +1075,7 @@ int smcrt_run_device(smcrt_scene* s, const smcrt_source* src, const smcrt_run_co
                      smcrt_device_tallies* dev, void* stream) {
   g_last_error.clear();
   if (!s || !src || !cfg || !dev) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
-  if (const int vst = voxel_flags_ok(s, cfg->flags)) return vst;
+  if (const int vst = sdfless_flags_ok(s, cfg->flags)) return vst;
   if (cfg->flags & SMCRT_FLAG_TRACK_PATHS)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
   if (cfg->flags & SMCRT_FLAG_PHASOR)
@@ -1125,7 +1164,7 @@ extern "C" {
 int smcrt_run(smcrt_scene* s, const smcrt_source* src, const smcrt_run_config* cfg, smcrt_tallies* io) {
   g_last_error.clear();
   if (!s || !src || !cfg || !io) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
-  if (const int vst = voxel_flags_ok(s, cfg->flags)) return vst;
+  if (const int vst = sdfless_flags_ok(s, cfg->flags)) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   const bool track = (cfg->flags & SMCRT_FLAG_TRACK_PATHS) != 0;
   if (track && !s->path_on)
@@ -1146,7 +1185,7 @@ int smcrt_run_origins(smcrt_scene* s, const smcrt_source* src, const double* ori
                       const smcrt_run_config* cfg, double* det_totals, smcrt_tallies* io) {
   g_last_error.clear();
   if (!s || !cfg || !io || (n_origins > 0 && !origins)) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
-  if (const int vst = smcrt::scene_refuse_voxel(s, "smcrt_run_origins")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(s, "smcrt_run_origins")) return vst;
   if (n_origins < 0) return fail(SMCRT_ERR_INVALID_ARG, "n_origins < 0");
   if (cfg->flags & SMCRT_FLAG_TRACK_PATHS)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
@@ -1225,6 +1264,16 @@ int smcrt_scene_classify(smcrt_scene* s, const double* points, int64_t n, int32_
       layer[i] = (ci < 1 || cj < 1 || ck < 1)
                      ? 0
                      : 1 + (int32_t)s->labels[(size_t)(ci - 1) + (size_t)s->grid.nx * ((size_t)(cj - 1) + (size_t)s->grid.ny * (size_t)(ck - 1))];
+      if (kappa) kappa[i] = layer[i] > 0 ? s->h_props[layer[i] - 1].kappa : 0.0;
+    }
+    return SMCRT_OK;
+  }
+  if (s->mesh) {  // a host cast along (0, 0, 1) and the emission rule; 0 outside the grid: host only
+    for (int64_t i = 0; i < n; ++i) {
+      const bool in = host_vox_of(points[3 * i], s->grid.nx, s->grid.xmax) >= 1 &&
+                      host_vox_of(points[3 * i + 1], s->grid.ny, s->grid.ymax) >= 1 &&
+                      host_vox_of(points[3 * i + 2], s->grid.nz, s->grid.zmax) >= 1;
+      layer[i] = in ? 1 + mesh_medium_at(*s, points + 3 * i) : 0;
       if (kappa) kappa[i] = layer[i] > 0 ? s->h_props[layer[i] - 1].kappa : 0.0;
     }
     return SMCRT_OK;
@@ -1325,7 +1374,7 @@ int smcrt_scene_deposit_regime(const smcrt_scene* s, int32_t* regime) {
 
 int smcrt_scene_invoxel_segments(smcrt_scene* s, int64_t* out) {
   if (!s || !out) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
-  if (const int vst = smcrt::scene_refuse_voxel(s, "smcrt_scene_invoxel_segments")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(s, "smcrt_scene_invoxel_segments")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   HIPCHK(hipSetDevice(s->device));
   unsigned long long n = 0;  // (a running total: segments of launches still running count later)
@@ -1344,7 +1393,7 @@ static void release_paths(smcrt_scene* s) {
 int smcrt_scene_set_path_tracking(smcrt_scene* s, const smcrt_path_config* cfg) {
   g_last_error.clear();
   if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
-  if (const int vst = smcrt::scene_refuse_voxel(s, "path tracking")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(s, "path tracking")) return vst;
   if (cfg) {  // (decided before any device call)
     if (cfg->max_vertices < 2 || cfg->max_vertices > 1024)
       return fail(SMCRT_ERR_INVALID_ARG, "path tracking: max_vertices must lie in 2 .. 1024");
@@ -1400,7 +1449,7 @@ int smcrt_scene_path_counts(smcrt_scene* s, int64_t* n_paths, int64_t* n_vertice
                             int64_t* n_truncated) {
   g_last_error.clear();
   if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
-  if (const int vst = smcrt::scene_refuse_voxel(s, "path tracking")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(s, "path tracking")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   unsigned long long ctl[3];
   std::vector<smcrt_path> hdr;
@@ -1417,7 +1466,7 @@ int smcrt_scene_path_counts(smcrt_scene* s, int64_t* n_paths, int64_t* n_vertice
 int smcrt_scene_read_paths(smcrt_scene* s, smcrt_path* paths, double* vertices) {
   g_last_error.clear();
   if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
-  if (const int vst = smcrt::scene_refuse_voxel(s, "path tracking")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(s, "path tracking")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   unsigned long long ctl[3];
   std::vector<smcrt_path> hdr;
@@ -1452,7 +1501,7 @@ int smcrt_scene_set_phasor(smcrt_scene* s, const smcrt_phasor_config* cfg) {
   if (cfg && cfg->fixed_k && !(cfg->wavenumber >= 0.0 && cfg->wavenumber <= 0x1.fffffffffffffp+1023))
     return fail(SMCRT_ERR_INVALID_ARG, "phasor: a fixed wavenumber must be finite and >= 0");  // (before any device call)
   if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
-  if (const int vst = smcrt::scene_refuse_voxel(s, "the phasor tally")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(s, "the phasor tally")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   HIPCHK(hipSetDevice(s->device));
   HIPCHK(hipStreamSynchronize(s->stream));  // (no launch of this scene may still use the grid)
@@ -1481,7 +1530,7 @@ int smcrt_scene_set_phasor(smcrt_scene* s, const smcrt_phasor_config* cfg) {
 int smcrt_scene_read_phasor(smcrt_scene* s, double* out) {
   g_last_error.clear();
   if (!s || !out) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
-  if (const int vst = smcrt::scene_refuse_voxel(s, "the phasor tally")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(s, "the phasor tally")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   if (!s->phasor_on) return fail(SMCRT_ERR_INVALID_ARG, "the phasor tally is not configured on this scene");
   HIPCHK(hipSetDevice(s->device));
@@ -1496,7 +1545,7 @@ int smcrt_scene_read_phasor(smcrt_scene* s, double* out) {
 int smcrt_scene_reset_phasor(smcrt_scene* s) {
   g_last_error.clear();
   if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
-  if (const int vst = smcrt::scene_refuse_voxel(s, "the phasor tally")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(s, "the phasor tally")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   if (!s->phasor_on) return fail(SMCRT_ERR_INVALID_ARG, "the phasor tally is not configured on this scene");
   HIPCHK(hipSetDevice(s->device));

@@ -93,7 +93,7 @@ int smcrt_spectral_sample(const smcrt_spectral* sp, int32_t mode, uint64_t seed,
 int smcrt_scene_set_spectral(smcrt_scene* scene, int32_t top_index, const smcrt_spectral* sp, int32_t mode,
                              uint64_t seed, uint64_t* draw, smcrt_optprops* out) {
   if (!scene || !draw) return set_error(SMCRT_ERR_INVALID_ARG, "NULL argument");
-  if (const int vst = smcrt::scene_refuse_voxel(scene, "smcrt_scene_set_spectral")) return vst;
+  if (const int vst = smcrt::scene_needs_sdf(scene, "smcrt_scene_set_spectral")) return vst;
   smcrt_optprops p;
   uint64_t d = *draw;  // the stream advances only if the layer took the result
   int st = smcrt_spectral_sample(sp, mode, seed, &d, &p);

@@ -27,6 +27,7 @@
 #include "geometry.h"
 #include "srcplan.h"
 #include "cull.h"
+#include "meshcast.h"
 
 namespace smcrt {
 
@@ -112,6 +113,13 @@ struct KCold {
   const uint8_t* vox_labels;  // [nx*ny*nz], x fastest as jmean: the medium of each voxel, 0-based
   uint32_t vox_n_media;       // media in K.props (== K.n_top)
   uint32_t vox_reserved;
+  // mesh media (read by mesh_kernel only, mesh.h; null / 0 otherwise). After the voxel fields, so
+  // that those stay where they were.
+  const MeshNode* mesh_nodes;  // the threaded hierarchy, depth-first order (meshcast.h)
+  const MeshTri* mesh_tris;    // the triangles in the hierarchy's order
+  const MeshFace* mesh_faces;  // normal and media of each triangle, by the caller's triangle index
+  uint32_t mesh_n_nodes;
+  uint32_t mesh_ambient;       // the medium of a point from which a cast meets nothing
 };
 
 // watchdog sites (KCold::watchdog bits 0-7; smcrt.hip names them)

@@ -17,7 +17,7 @@ import threading
 import numpy as np
 
 from . import abi
-from .scene import Mono, VoxelScene, detector_array
+from .scene import MeshScene, Mono, VoxelScene, detector_array
 from .tallies import Result
 
 LIB_PATH = os.environ.get("SMCRT_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsmcrt.so")
@@ -47,6 +47,10 @@ def load_library(path: str = LIB_PATH):
         L.smcrt_voxel_scene_create.argtypes = [C.POINTER(C.c_uint8), C.POINTER(abi.Medium), C.c_int32,
                                                C.POINTER(abi.Grid), C.POINTER(abi.Detector), C.c_int32, C.c_int32,
                                                C.POINTER(C.c_void_p)]
+        L.smcrt_mesh_scene_create.argtypes = [C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_uint8), C.c_int32, C.POINTER(abi.Medium), C.c_int32,
+                                              C.c_int32, C.POINTER(abi.Grid), C.POINTER(abi.Detector), C.c_int32,
+                                              C.c_int32, C.POINTER(C.c_void_p)]
         L.smcrt_scene_destroy.argtypes = [C.c_void_p]
         L.smcrt_scene_destroy.restype = None
         L.smcrt_scene_det_bins.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
@@ -144,6 +148,14 @@ class Engine:
             _check(L.smcrt_voxel_scene_create(scene.labels.ctypes.data_as(C.POINTER(C.c_uint8)), self._media,
                                               scene.n_media, C.byref(grid), self._darr, len(self.dets), device,
                                               C.byref(h)))
+        elif isinstance(scene, MeshScene):  # closed triangle surfaces (smcrt_mesh_scene_create)
+            scene.check_grid(grid)
+            self._media = scene.media_array()
+            _check(L.smcrt_mesh_scene_create(scene.verts.ctypes.data_as(C.POINTER(C.c_double)), len(scene.verts),
+                                             scene.tris.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             scene.tri_media.ctypes.data_as(C.POINTER(C.c_uint8)), len(scene.tris),
+                                             self._media, scene.n_media, scene.ambient, C.byref(grid), self._darr,
+                                             len(self.dets), device, C.byref(h)))
         else:
             self._nodes = scene.node_array()
             self._top = scene.top_array()
@@ -234,6 +246,8 @@ class Engine:
         runs the scene's voxel twin."""
         if isinstance(self.scene, VoxelScene):
             raise ValueError("voxelise() is for an SDF scene; this engine already runs a voxel scene")
+        if isinstance(self.scene, MeshScene):
+            raise ValueError("voxelise() is for an SDF scene; this engine runs a mesh scene")
         g = self.grid
         cx, cy, cz = [(np.arange(n) + 0.5) * (2.0 * m / n) - m for n, m in ((g.nx, g.xmax), (g.ny, g.ymax), (g.nz, g.zmax))]
         pts = np.stack(np.meshgrid(cz, cy, cx, indexing="ij")[::-1], axis=-1).reshape(-1, 3)  # x fastest

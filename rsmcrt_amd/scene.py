@@ -453,6 +453,80 @@ class VoxelScene:
         return arr
 
 
+class MeshScene:
+    """Closed triangle surfaces between media (smcrt_mesh_scene_create): `media` is a list of optical
+    properties (`mono(...)`), `ambient` the index of the medium of a point from which a ray meets no
+    surface. `add_surface` appends one closed, outward-oriented surface; Engine(mesh_scene, grid,
+    dets) runs the scene. Vertices are in the centred coordinates of sources and detectors."""
+
+    def __init__(self, media, ambient=0):
+        self.media = list(media)
+        if not 1 <= len(self.media) <= 256:
+            raise ValueError(f"a mesh scene takes 1 .. 256 media, not {len(self.media)}")
+        if not 0 <= int(ambient) < len(self.media):
+            raise ValueError(f"ambient = {ambient} is not an index into {len(self.media)} media")
+        self.ambient = int(ambient)
+        self.verts = np.zeros((0, 3), dtype=np.float64)
+        self.tris = np.zeros((0, 3), dtype=np.int32)
+        self.tri_media = np.zeros((0, 2), dtype=np.uint8)  # (outside, inside) of each triangle
+
+    @property
+    def n_media(self) -> int:
+        return len(self.media)
+
+    def add_surface(self, verts, tris, inside, outside):
+        """Append the surface (verts (nv, 3), tris (nt, 3) indexing them, normals pointing out of
+        it): medium `inside` within, medium `outside` around it. Returns self."""
+        v = np.asarray(verts, dtype=np.float64)
+        t = np.asarray(tris)
+        if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3 or len(t) == 0:
+            raise ValueError(f"verts must have shape (nv, 3) and tris (nt, 3), not {v.shape} and {t.shape}")
+        if not np.issubdtype(t.dtype, np.integer):
+            raise ValueError("tris must hold integers")
+        if t.min() < 0 or t.max() >= len(v):
+            raise ValueError(f"tris index vertices 0 .. {len(v) - 1}, not {int(t.min())} .. {int(t.max())}")
+        for name, m in (("inside", inside), ("outside", outside)):
+            if not 0 <= int(m) < self.n_media:
+                raise ValueError(f"{name} = {m} is not an index into {self.n_media} media")
+        self.tris = np.ascontiguousarray(np.vstack([self.tris, t.astype(np.int32) + len(self.verts)]))
+        self.verts = np.ascontiguousarray(np.vstack([self.verts, v]))
+        pair = np.tile(np.array([[int(outside), int(inside)]], dtype=np.uint8), (len(t), 1))
+        self.tri_media = np.ascontiguousarray(np.vstack([self.tri_media, pair]))
+        return self
+
+    def add_obj(self, path, inside, outside):
+        """Append the surface of an ASCII Wavefront OBJ file: its `v` and `f` lines (polygons become
+        fans; `a/b/c` and negative indices are handled), everything else is ignored."""
+        verts, tris = [], []
+        with open(path) as f:
+            for line in f:
+                w = line.split()
+                if not w:
+                    continue
+                if w[0] == "v":
+                    verts.append([float(x) for x in w[1:4]])
+                elif w[0] == "f":
+                    idx = [int(x.split("/")[0]) for x in w[1:]]
+                    idx = [i - 1 if i > 0 else len(verts) + i for i in idx]
+                    tris.extend([idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1))
+        if not tris:
+            raise ValueError(f"{path}: no faces")
+        return self.add_surface(np.array(verts, dtype=np.float64).reshape(-1, 3), np.array(tris, dtype=np.int64),
+                                inside, outside)
+
+    def check_grid(self, g) -> None:
+        """The world ends at the grid, so a surface may reach beyond it (a slab wider than the grid),
+        as smcrt_mesh_scene_create allows; only a scene without any surface is refused here."""
+        if len(self.tris) == 0:
+            raise ValueError("the mesh scene has no surface")
+
+    def media_array(self):
+        arr = (abi.Medium * len(self.media))()
+        for i, o in enumerate(self.media):
+            arr[i].mus, arr[i].mua, arr[i].hgg, arr[i].n = float(o.mus), float(o.mua), float(o.hgg), float(o.n)
+        return arr
+
+
 # ------------------------------------------------------------------ grid ----------
 def grid(nx, ny, nz, xmax, ymax, zmax) -> abi.Grid:
     g = abi.Grid()
