@@ -42,6 +42,8 @@ module smcrt_mod
         SMCRT_FLAG_RECORD_PHOTONS = 32, SMCRT_FLAG_ASYNC_FOLD = 64, SMCRT_FLAG_OVERLAP = 128
     ! smcrt_run only, on a scene configured with smcrt_scene_set_phasor: the complex phasor grid
     integer(c_int32_t), parameter :: SMCRT_FLAG_PHASOR = 512
+    ! smcrt_phasor_config%reserved, bit 0: the phase is an optical path length (n * length per piece)
+    integer(c_int32_t), parameter :: SMCRT_PHASOR_OPTICAL_PATH = 1
     integer, parameter :: SMCRT_NCOUNTERS = 16
     ! multi-GPU: packed-tally fields (smcrt_pack_layout%fields), all visible devices
     integer(c_int32_t), parameter :: SMCRT_PACK_JMEAN = 1, SMCRT_PACK_ABSORB = 2, SMCRT_PACK_EMISSION = 4, &
@@ -164,6 +166,11 @@ module smcrt_mod
         real(c_double)     :: wavenumber = 0._c_double  ! with fixed_k /= 0: every photon's k
     end type smcrt_phasor_config
 
+    type, bind(C) :: smcrt_screen                 ! a field screen (smcrt.h "field screens")
+        real(c_double)     :: origin(3) = 0._c_double, eu(3) = 0._c_double, ev(3) = 0._c_double
+        integer(c_int32_t) :: nu = 1, nv = 1, sides = 0, reserved = 0
+    end type smcrt_screen
+
     interface
         integer(c_int) function smcrt_abi_version() bind(C, name="smcrt_abi_version")
             import :: c_int
@@ -227,6 +234,42 @@ module smcrt_mod
             import :: c_int, c_ptr
             type(c_ptr), value :: scene
         end function smcrt_scene_reset_phasor
+
+        ! screens: c_loc of an array of n smcrt_screen (target), or c_null_ptr / 0 to turn them off
+        integer(c_int) function smcrt_scene_set_screens(scene, screens, n) bind(C, name="smcrt_scene_set_screens")
+            import :: c_int, c_int32_t, c_ptr
+            type(c_ptr), value        :: scene, screens
+            integer(c_int32_t), value :: n
+        end function smcrt_scene_set_screens
+
+        integer(c_int) function smcrt_scene_screen_info(scene, n, n_doubles) bind(C, name="smcrt_scene_screen_info")
+            import :: c_int, c_int32_t, c_int64_t, c_ptr
+            type(c_ptr), value              :: scene
+            integer(c_int32_t), intent(out) :: n
+            integer(c_int64_t), intent(out) :: n_doubles
+        end function smcrt_scene_screen_info
+
+        ! adds the fields into field(n_doubles / 2) (complex(c_double_complex): re, im interleaved)
+        integer(c_int) function smcrt_scene_read_screens(scene, field) bind(C, name="smcrt_scene_read_screens")
+            import :: c_int, c_ptr, c_double_complex
+            type(c_ptr), value                        :: scene
+            complex(c_double_complex), intent(inout)  :: field(*)
+        end function smcrt_scene_read_screens
+
+        integer(c_int) function smcrt_scene_reset_screens(scene) bind(C, name="smcrt_scene_reset_screens")
+            import :: c_int, c_ptr
+            type(c_ptr), value :: scene
+        end function smcrt_scene_reset_screens
+
+        ! the hit rule on the host: 1 hit (t, pixel set), 0 miss, < 0 error
+        integer(c_int) function smcrt_screen_hit(screen, start, dir, sep, t, pixel) bind(C, name="smcrt_screen_hit")
+            import :: c_int, c_int32_t, c_double, smcrt_screen
+            type(smcrt_screen), intent(in)  :: screen
+            real(c_double), intent(in)      :: start(3), dir(3)
+            real(c_double), value           :: sep
+            real(c_double), intent(out)     :: t
+            integer(c_int32_t), intent(out) :: pixel
+        end function smcrt_screen_hit
 
         integer(c_int) function smcrt_scene_check(scene) bind(C, name="smcrt_scene_check")
             import :: c_int, c_ptr

@@ -574,9 +574,16 @@ int smcrt_scene_read_paths(smcrt_scene* scene, smcrt_path* paths, double* vertic
  * of a phasor run is that of the same run without the flag. */
 typedef struct smcrt_phasor_config {
   int32_t fixed_k;   /* != 0: every photon's k is `wavenumber` */
-  int32_t reserved;
+  int32_t reserved;  /* bit 0: SMCRT_PHASOR_OPTICAL_PATH; the other bits 0 (else SMCRT_ERR_INVALID_ARG) */
   double wavenumber; /* with fixed_k: finite and >= 0 (0 makes the tally a real crossing count) */
 } smcrt_phasor_config;
+/* smcrt_phasor_config.reserved, bit 0: the phase is an optical path length. A voxel piece of
+ * length dc then adds n * dc to the phase instead of dc, n being the refractive index of the
+ * layer the photon carries while the piece is walked (the layer whose mua the reference hands
+ * update_grids for that segment). The emitters' start phase is unchanged. The option applies to
+ * the phase itself, so the phasor grid and the field screens below both see it. Without the bit
+ * the phase is the geometric length it always was. */
+#define SMCRT_PHASOR_OPTICAL_PATH 1
 
 /* Configure (allocating and zeroing the grid) or, with cfg NULL, turn off and free the phasor
  * tally of a scene. SMCRT_ERR_OOM if the grid does not fit. */
@@ -585,6 +592,61 @@ int smcrt_scene_set_phasor(smcrt_scene* scene, const smcrt_phasor_config* cfg);
 int smcrt_scene_read_phasor(smcrt_scene* scene, double* out);
 /* Zero the grid. */
 int smcrt_scene_reset_phasor(smcrt_scene* scene);
+
+/* ---- field screens (the reference's open "phase screen detector"; SDF scenes only) -------------
+ * A screen is a rectangle that records the complex amplitude of the photons crossing it. Screens
+ * are tallied only by a run with SMCRT_FLAG_PHASOR, which supplies k and the optical-path option
+ * (so that run needs smcrt_scene_set_phasor; screens may be configured before or after it). A
+ * phasor run without screens, and any run without the flag, is what it is without them.
+ *
+ * The hit rule, for one leg (start, dir, sep): the straight stretch between two events of a photon
+ * (emission, interaction, reflection, surface crossing), the very leg the detectors receive. With
+ * N = normalise(eu x ev), every product in fp64 without fused multiply-add, dot(a, b) =
+ * a.x*b.x + a.y*b.y + a.z*b.z summed left to right:
+ *   den = dot(dir, N)                    den == 0: miss; sides +1 needs den > 0, sides -1 den < 0
+ *   t   = dot(origin - start, N) / den   a hit needs 0 < t <= sep (a crossing exactly at a leg's end
+ *                                        belongs to that leg, not to the next one)
+ *   w   = (start + t*dir) - origin
+ *   u   = dot(w, eu) / dot(eu, eu),  v = dot(w, ev) / dot(ev, ev)   a hit needs 0 <= u < 1, 0 <= v < 1
+ *   iu  = min((int)(u * nu), nu - 1),  iv likewise
+ * A hit adds weight * (cos(k phi), sin(k phi)) to pixel (iu, iv), with phi = the photon's phase at
+ * the leg's start + n_leg * t; n_leg is 1, or with SMCRT_PHASOR_OPTICAL_PATH the refractive index
+ * of the layer the photon carries when the leg is recorded. The phase is taken forward from the
+ * leg's start, so it is right for a leg that leaves the grid and does not depend on where the
+ * sphere trace stopped. Screens belong inside the grid: a leg is followed at least to the grid's
+ * wall, and beyond it only as far as the trace went. The rule takes `dir` for a unit vector, as
+ * the detectors do: t and sep are then lengths. A source that keeps a direction as given (the
+ * disc source, as in the reference) should be given a unit vector when screens are read.
+ *
+ * Storage: fp64, (re, im) interleaved; pixel (iu, iv) of a screen at 2 * (iu + nu * iv); the
+ * screens are concatenated in the order given, n_doubles = 2 * sum(nu * nv). The buffer lives on
+ * the scene's device, accumulates over runs and is summed with atomics.
+ *
+ * smcrt_scene_set_screens validates on the host before any device call and names the first
+ * offending screen: 1 <= n <= 16; every number finite; |eu|, |ev| > 0; |eu . ev| <= 1e-12 |eu| |ev|;
+ * 1 <= nu, nv <= 4096; sides in {-1, 0, 1}; reserved == 0 (else SMCRT_ERR_INVALID_ARG). A voxel or
+ * mesh scene answers SMCRT_ERR_UNSUPPORTED, a buffer that does not fit SMCRT_ERR_OOM. */
+typedef struct smcrt_screen {      /* 88 bytes */
+  double origin[3];                /* one corner */
+  double eu[3], ev[3];             /* the two edges from that corner, orthogonal */
+  int32_t nu, nv;                  /* pixels along eu, ev */
+  int32_t sides;                   /* 0 both; +1 only dir.N > 0; -1 only dir.N < 0; N = normalise(eu x ev) */
+  int32_t reserved;                /* 0 */
+} smcrt_screen;
+
+/* Configure (allocating and zeroing the field buffer) or, with screens NULL / n 0, turn off and
+ * free the screens of a scene. */
+int smcrt_scene_set_screens(smcrt_scene* scene, const smcrt_screen* screens, int32_t n);
+/* The number of screens and of doubles smcrt_scene_read_screens adds (either may be NULL). */
+int smcrt_scene_screen_info(const smcrt_scene* scene, int32_t* n, int64_t* n_doubles);
+/* Wait for the scene's runs and ADD the field buffer into out[n_doubles]. */
+int smcrt_scene_read_screens(smcrt_scene* scene, double* out);
+/* Zero the field buffer. */
+int smcrt_scene_reset_screens(smcrt_scene* scene);
+/* The hit rule on the host, the text the kernel runs: 1 and *t, *pixel (iu + nu * iv) for a hit,
+ * 0 for a miss (t and pixel untouched), < 0 for an invalid screen or a NULL argument. */
+int smcrt_screen_hit(const smcrt_screen* screen, const double start[3], const double dir[3], double sep,
+                     double* t, int32_t* pixel);
 
 /* Device-resident variant for multi-GPU and benchmarking: launches on `stream`
  * (a hipStream_t; NULL = the legacy default stream) and accumulates into caller-owned

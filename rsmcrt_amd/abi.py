@@ -70,6 +70,9 @@ DEPOSIT_REGIMES = {DEPOSIT_ATOMIC: "atomic", DEPOSIT_SORTED: "sorted", DEPOSIT_B
 # smcrt_detector.reserved, bit 0: the detector files the photon's path at every hit it scores
 DET_TRACK_HISTORY = 1
 
+# smcrt_phasor_config.reserved, bit 0: a voxel piece adds n * length to the phase (optical path)
+PHASOR_OPTICAL_PATH = 1
+
 # counters
 COUNTER_NAMES = [
     "photons", "emit_retries", "scatters", "absorbed", "sdf_evals", "deposits",
@@ -196,6 +199,11 @@ class PhasorConfig(C.Structure):
     _fields_ = [("fixed_k", C.c_int32), ("reserved", C.c_int32), ("wavenumber", C.c_double)]
 
 
+class Screen(C.Structure):  # smcrt_screen: a field screen (scene.screen, Engine.set_screens)
+    _fields_ = [("origin", C.c_double * 3), ("eu", C.c_double * 3), ("ev", C.c_double * 3),
+                ("nu", C.c_int32), ("nv", C.c_int32), ("sides", C.c_int32), ("reserved", C.c_int32)]
+
+
 # smcrt_path as a numpy dtype (same layout)
 def path_dtype():
     import numpy as np
@@ -278,6 +286,8 @@ EXPORTED_SYMBOLS = [
     "smcrt_scene_set_path_tracking", "smcrt_scene_path_counts", "smcrt_scene_read_paths", "smcrt_write_paths",
     "smcrt_job_history_filename",
     "smcrt_scene_set_phasor", "smcrt_scene_read_phasor", "smcrt_scene_reset_phasor",
+    "smcrt_scene_set_screens", "smcrt_scene_screen_info", "smcrt_scene_read_screens", "smcrt_scene_reset_screens",
+    "smcrt_screen_hit",
     "smcrt_displacement_compile", "smcrt_displacement_eval", "smcrt_displacement_describe",
     "smcrt_voxel_scene_create", "smcrt_scene_deposit_regime",
     "smcrt_mesh_scene_create",

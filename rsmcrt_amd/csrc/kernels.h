@@ -124,6 +124,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
     hist_off = np + nf;
   }
   double* const startp = sh_dyn + hist_off + threadIdx.x;  // [3][256] when n_dets > 0
+  // PHAS: the screen count and the optical-path option, wave-uniform (phasor.h). A launch with
+  // screens keeps the leg's start point too, and in a fourth row the phase there.
+  [[maybe_unused]] std::conditional_t<PHAS, PhasWave, NoPhasWave> PW;
+  if constexpr (PHAS) {
+    PW.n_scr = C->n_screens;
+    PW.optical = C->phasor_optical;
+    if (PW.n_scr) hist_off += (K.n_dets ? 0 : 3 * 256) + 256;
+  }
   if (K.n_dets) hist_off += 3 * 256;
   // deposit state: the sorted path's per-wave tile histogram (hist_tiles words) or the
   // bucketed path's per-block word per tile (cur | next | fill: 2 * bucket_tiles words)
@@ -363,6 +371,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
             if constexpr (PHAS) {
               DdaPiece pc;
               if (lane_id == ow) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight, &pc);
+              if (PW.optical) pc.dc = phas_index(K, props, dep, L.layer) * pc.dc;  // (wave-uniform: off, the piece is untouched)
               phasor_piece(K, C, PH, pc, dep, vox, L.weight);
             } else {
               if (lane_id == ow) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight);
@@ -573,6 +582,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
             L.dir = L.dir - smul(s2, N);
             LCTR(LC_REFL)++;
             if (K.n_dets) { startp[0] = L.pos.x; startp[256] = L.pos.y; startp[512] = L.pos.z; }
+            if constexpr (PHAS) {
+              if (PW.n_scr) { startp[0] = L.pos.x; startp[256] = L.pos.y; startp[512] = L.pos.z; startp[768] = PH.phase; }
+            }
             if (++LU(LU_BOUNCES) > 1000) {  // :313-315: return without write-back
               LCTR(LC_BABORT)++;
               L.pos = v3(sh->entry[0][threadIdx.x], sh->entry[1][threadIdx.x], sh->entry[2][threadIdx.x]);
@@ -638,6 +650,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
         if constexpr (PHAS) {
           DdaPiece pc;
           if (L.seg) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight, &pc);
+          if (PW.optical) pc.dc = phas_index(K, props, dep, L.layer) * pc.dc;  // (wave-uniform: off, the piece is untouched)
           phasor_piece(K, C, PH, pc, dep, vox, L.weight);
         } else {
           if (L.seg) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight);
@@ -659,6 +672,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
     bool rec = false;
     V3 rec_start = v3(0.0, 0.0, 0.0);
     double rec_sep = 0.0;
+    [[maybe_unused]] std::conditional_t<PHAS, double, NoPhasWave> rec_phase{};  // PHAS with screens: the phase at rec_start
     if (!L.seg && (L.st == ST_H2 || L.st == ST_B0 || L.st == ST_X1)) {
       if (L.st == ST_X1) {  // :294-303 / :326-335
         L.taurun = L.taurun + L.d * props[L.layer - 1].kappa;
@@ -669,6 +683,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
         rec_start = v3(startp[0], startp[256], startp[512]);
         rec_sep = pointsep(L.pos, rec_start);
         startp[0] = L.pos.x; startp[256] = L.pos.y; startp[512] = L.pos.z;
+      }
+      if constexpr (PHAS) {
+        if (PW.n_scr) {  // the same leg for the screens, and the phase at its start
+          if (!K.n_dets) {
+            rec_start = v3(startp[0], startp[256], startp[512]);
+            rec_sep = pointsep(L.pos, rec_start);
+            startp[0] = L.pos.x; startp[256] = L.pos.y; startp[512] = L.pos.z;
+          }
+          rec_phase = startp[768];
+          startp[768] = PH.phase;
+        }
       }
       if (L.st == ST_H2) {
         L.st = ST_H3; L.pend = true;
@@ -699,6 +724,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
       } else {
         LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, rec_start, L.dir, rec_sep, L.layer, L.weight, tot);
       }
+    }
+
+    if constexpr (PHAS) {  // the field screens see the same leg (phasor.h)
+      if (PW.n_scr && rec)
+        screen_hits(C, PW.n_scr, rec_start, L.dir, rec_sep, rec_phase, PW.optical ? phas_index(K, props, true, L.layer) : 1.0,
+                    PH.k, L.weight);
     }
 
     // ---- P6: tauint2 write-back checks, :341-362 -----------------------------------------
@@ -776,6 +807,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
         }
         if (L.st == ST_T2) {  // tauint2 entry, inttau2.f90:48-60
           if (K.n_dets) { startp[0] = L.pos.x; startp[256] = L.pos.y; startp[512] = L.pos.z; }
+          if constexpr (PHAS) {
+            if (PW.n_scr) { startp[0] = L.pos.x; startp[256] = L.pos.y; startp[512] = L.pos.z; startp[768] = PH.phase; }
+          }
           sh->entry[0][threadIdx.x] = L.pos.x; sh->entry[1][threadIdx.x] = L.pos.y;
           sh->entry[2][threadIdx.x] = L.pos.z; sh->entry[3][threadIdx.x] = L.dir.x;
           sh->entry[4][threadIdx.x] = L.dir.y; sh->entry[5][threadIdx.x] = L.dir.z;

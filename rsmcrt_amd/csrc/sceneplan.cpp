@@ -629,4 +629,43 @@ int32_t mesh_medium_at(const ScenePlan& p, const double pt[3]) {
   return (int32_t)((d[0] * F.N[0] + d[1] * F.N[1] + d[2] * F.N[2]) > 0.0 ? F.inside : F.outside);
 }
 
+int plan_screens(const smcrt_screen* screens, int32_t n, std::vector<ScreenDev>* out, int64_t* n_doubles) {
+  if (!screens || !out || !n_doubles) return fail(SMCRT_ERR_INVALID_ARG, "screens: NULL argument");
+  if (n < 1 || n > SCREEN_MAX)
+    return fail(SMCRT_ERR_INVALID_ARG, "screens: " + std::to_string(n) + " screens (1 to " + std::to_string(SCREEN_MAX) + ")");
+  out->clear();
+  int64_t off = 0;
+  for (int32_t i = 0; i < n; ++i) {
+    const smcrt_screen& s = screens[i];
+    const std::string who = "screen " + std::to_string(i) + ": ";
+    for (int a = 0; a < 3; ++a)
+      if (!std::isfinite(s.origin[a]) || !std::isfinite(s.eu[a]) || !std::isfinite(s.ev[a]))
+        return fail(SMCRT_ERR_INVALID_ARG, who + "origin, eu and ev must be finite");
+    const V3 eu = v3(s.eu[0], s.eu[1], s.eu[2]), ev = v3(s.ev[0], s.ev[1], s.ev[2]);
+    const double uu = dot(eu, eu), vv = dot(ev, ev);
+    if (!(uu > 0.0) || !(vv > 0.0) || !std::isfinite(uu) || !std::isfinite(vv))
+      return fail(SMCRT_ERR_INVALID_ARG, who + "eu and ev must have a length above 0 (and a finite square)");
+    if (!(std::fabs(dot(eu, ev)) <= 1e-12 * (std::sqrt(uu) * std::sqrt(vv))))
+      return fail(SMCRT_ERR_INVALID_ARG, who + "eu and ev must be orthogonal (|eu . ev| <= 1e-12 |eu| |ev|)");
+    if (s.nu < 1 || s.nu > SCREEN_MAX_PIXELS || s.nv < 1 || s.nv > SCREEN_MAX_PIXELS)
+      return fail(SMCRT_ERR_INVALID_ARG, who + "nu and nv must be 1 to " + std::to_string(SCREEN_MAX_PIXELS));
+    if (s.sides < -1 || s.sides > 1) return fail(SMCRT_ERR_INVALID_ARG, who + "sides must be -1, 0 or 1");
+    if (s.reserved != 0) return fail(SMCRT_ERR_INVALID_ARG, who + "reserved must be 0");
+    const V3 c = v3(eu.y * ev.z - eu.z * ev.y, eu.z * ev.x - eu.x * ev.z, eu.x * ev.y - eu.y * ev.x);
+    const double lc = len(c);
+    if (!(lc > 0.0) || !std::isfinite(lc))
+      return fail(SMCRT_ERR_INVALID_ARG, who + "eu x ev must have a finite length above 0");
+    ScreenDev d{};
+    for (int a = 0; a < 3; ++a) { d.origin[a] = s.origin[a]; d.eu[a] = s.eu[a]; d.ev[a] = s.ev[a]; }
+    d.N[0] = c.x / lc; d.N[1] = c.y / lc; d.N[2] = c.z / lc;
+    d.uu = uu; d.vv = vv;
+    d.nu = s.nu; d.nv = s.nv; d.sides = s.sides; d.reserved = 0;
+    d.offset = (uint64_t)off;
+    off += 2 * (int64_t)s.nu * (int64_t)s.nv;
+    out->push_back(d);
+  }
+  *n_doubles = off;
+  return SMCRT_OK;
+}
+
 }  // namespace smcrt

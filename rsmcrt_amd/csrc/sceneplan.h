@@ -194,6 +194,13 @@ int32_t mesh_medium_at(const ScenePlan& p, const double pt[3]);
 // Dynamic LDS of mesh_kernel (mesh.h): voxel_kernel's layout
 inline size_t mesh_lds(const ScenePlan& p, uint32_t dep_words) { return voxel_lds(p, dep_words); }
 
+// Field screens (smcrt_scene_set_screens, smcrt_screen_hit): validates smcrt.h's list (1 <= n <= 16,
+// finite numbers, non-zero orthogonal edges, 1 <= nu, nv <= 4096, sides, reserved), naming the
+// first offending screen, and fills what the hit rule reads (screen.h): N, dot(eu, eu), dot(ev, ev)
+// and each screen's offset in the field buffer; *n_doubles is the buffer's size. Same return
+// convention as plan_scene.
+int plan_screens(const smcrt_screen* screens, int32_t n, std::vector<ScreenDev>* out, int64_t* n_doubles);
+
 // ---- pure rules of the launch path ----
 // the lean path's dynamic LDS (ws_kernel): staged props + faces, then the block's bucket words
 inline size_t lean_lds(const ScenePlan& p) {
@@ -205,12 +212,15 @@ inline uint32_t dep_words(const ScenePlan& p) { return p.bucketed ? 2 * p.n_tile
 // Dynamic LDS of the transport kernel: staged props + faces, detector start points, then the
 // deposit words, then the coop table.
 // (`hist`: also the phasor tally's instantiations, which keep their faces there too)
-inline size_t transport_lds(const ScenePlan& p, uint32_t dep_words, bool xsrc, bool hist = false) {
+// (`screens`: a phasor launch that tallies field screens keeps the start points whether or not the
+// scene has detectors, and a fourth row: the phase there)
+inline size_t transport_lds(const ScenePlan& p, uint32_t dep_words, bool xsrc, bool hist = false, bool screens = false) {
   const bool ctab = !p.ctab.empty() && p.coop_lanes > 0;  // the COOP instantiations stage it
   // (the general emitter with the COOP machinery and the path recorder keep their faces in
   // device memory, kernel_ptrs.h)
   const bool faces = p.lds_faces && !(xsrc && p.coop_lanes > 0) && !hist;
-  return (faces ? p.face_bytes : 0) + (p.n_dets ? 3 * 256 * sizeof(double) : 0) +
+  const size_t start_rows = screens ? 4 : p.n_dets ? 3 : 0;
+  return (faces ? p.face_bytes : 0) + start_rows * 256 * sizeof(double) +
          (size_t)dep_words * sizeof(uint32_t) + (ctab ? CTAB_DOUBLES * sizeof(double) : 0);
 }
 // Pool records that a launch of `blocks` transport blocks does not fill: per wave, the last

@@ -188,6 +188,13 @@ struct smcrt_scene : ScenePlan {
   smcrt_phasor_config phasor_cfg{};
   DevBuf<double> d_phasor;
   int grid_blocks_phas[2] = {0, 0};  // the PHAS instantiations' grids (plain, XSRC)
+  // field screens (smcrt_scene_set_screens; screen.h): the table and the field buffer, tallied by
+  // phasor launches only; such a launch holds a fourth row of start-point LDS, hence grids of its own
+  std::vector<ScreenDev> screens;
+  int64_t screen_doubles = 0;
+  DevBuf<ScreenDev> d_screens;
+  DevBuf<double> d_screen_field;
+  int grid_blocks_phas_scr[2] = {0, 0};
   std::mutex mu;
 };
 
@@ -701,10 +708,13 @@ static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xs
   const uint64_t ws_needed = (Ch.n_photons + kinst_ws_photon_lanes() - 1) / kinst_ws_photon_lanes();
   const bool hist = (K.flags & SMCRT_FLAG_TRACK_PATHS) && s->path_on;  // (never lean: launch_lean)
   const bool phas = (K.flags & SMCRT_FLAG_PHASOR) && s->phasor_on && !hist;  // (likewise; never with hist: smcrt_run)
+  // (the kernel sizes its start-point rows by the very count it reads from this KCold)
+  const bool scr = phas && Ch.n_screens > 0;
   const int blocks = (int)std::min<uint64_t>(
       (uint64_t)(lean ? s->grid_blocks_ws
                       : hist ? s->grid_blocks_hist[xsrc ? 1 : 0]
-                             : phas ? s->grid_blocks_phas[xsrc ? 1 : 0] : (xsrc ? s->grid_blocks_x : s->grid_blocks)),
+                             : scr ? s->grid_blocks_phas_scr[xsrc ? 1 : 0]
+                                   : phas ? s->grid_blocks_phas[xsrc ? 1 : 0] : (xsrc ? s->grid_blocks_x : s->grid_blocks)),
       std::max<uint64_t>(1, lean ? ws_needed : blocks_needed));
   const smcrt_sdf_node* a_nodes = K.nodes;
   const ProgOp* a_prog = K.prog;
@@ -727,7 +737,7 @@ static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xs
     const int64_t* a_off = K.det_off;
     void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&a_dets, (void*)&a_off, (void*)&C};
     HIPCHK(hipLaunchKernel(transport_fn(s, xsrc, hist, phas), dim3(blocks), dim3(256), args,
-                           transport_lds(*s, dep_words(*s), xsrc, hist || phas), stream));
+                           transport_lds(*s, dep_words(*s), xsrc, hist || phas, scr), stream));
   }
   HIPCHK(hipGetLastError());
   if (ev) HIPCHK(hipEventRecord(ev[1], stream));
@@ -922,6 +932,13 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.phasor_k = !phas ? 0.0
                 : s->phasor_cfg.fixed_k ? s->phasor_cfg.wavenumber
                                         : 6.283185307179586 / (src->spectrum ? src->spectrum->wavelength : 500.0);
+  // field screens and the optical-path option: a phasor launch only (a voxel or a mesh scene
+  // has neither: smcrt_scene_set_phasor and smcrt_scene_set_screens refuse them)
+  const bool scr = phas && !s->screens.empty() && s->d_screens && s->d_screen_field;
+  Ch.screens = scr ? (const ScreenDev*)s->d_screens : nullptr;
+  Ch.screen_field = scr ? (double*)s->d_screen_field : nullptr;
+  Ch.n_screens = scr ? (uint32_t)s->screens.size() : 0u;
+  Ch.phasor_optical = phas && (s->phasor_cfg.reserved & SMCRT_PHASOR_OPTICAL_PATH) ? 1u : 0u;
   Ch.vox_labels = s->d_labels;
   Ch.vox_n_media = s->voxel ? (uint32_t)s->n_top : 0u;
   Ch.vox_reserved = 0;
@@ -1496,10 +1513,25 @@ int smcrt_scene_read_paths(smcrt_scene* s, smcrt_path* paths, double* vertices) 
 }
 
 // ---- the phasor tally (phasor.h) ----------------------------------------------------
+// The persistent grids of the PHAS instantiations (plain, XSRC), without and with the screens'
+// rows of start-point LDS.
+static void phas_grids(smcrt_scene* s) {
+  for (int scr = 0; scr < 2; ++scr)
+    for (int x = 0; x < 2; ++x) {
+      int per_cu = 0;
+      const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &per_cu, transport_fn(s, x == 1, false, true), 256, transport_lds(*s, dep_words(*s), x == 1, true, scr == 1));
+      if (oe != hipSuccess || per_cu < 1) per_cu = 1;
+      (scr ? s->grid_blocks_phas_scr : s->grid_blocks_phas)[x] = s->n_cus * per_cu;
+    }
+}
+
 int smcrt_scene_set_phasor(smcrt_scene* s, const smcrt_phasor_config* cfg) {
   g_last_error.clear();
   if (cfg && cfg->fixed_k && !(cfg->wavenumber >= 0.0 && cfg->wavenumber <= 0x1.fffffffffffffp+1023))
     return fail(SMCRT_ERR_INVALID_ARG, "phasor: a fixed wavenumber must be finite and >= 0");  // (before any device call)
+  if (cfg && (cfg->reserved & ~SMCRT_PHASOR_OPTICAL_PATH))
+    return fail(SMCRT_ERR_INVALID_ARG, "phasor: reserved has bits set other than SMCRT_PHASOR_OPTICAL_PATH");
   if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
   if (const int vst = smcrt::scene_needs_sdf(s, "the phasor tally")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
@@ -1508,13 +1540,7 @@ int smcrt_scene_set_phasor(smcrt_scene* s, const smcrt_phasor_config* cfg) {
   s->phasor_on = false;
   s->d_phasor.reset();
   if (!cfg) return SMCRT_OK;
-  for (int x = 0; x < 2; ++x) {  // the PHAS instantiations' persistent grids
-    int per_cu = 0;
-    const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, transport_fn(s, x == 1, false, true), 256, transport_lds(*s, dep_words(*s), x == 1, true));
-    if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-    s->grid_blocks_phas[x] = s->n_cus * per_cu;
-  }
+  phas_grids(s);
   const size_t n2 = 2 * (size_t)s->grid.nx * (size_t)s->grid.ny * (size_t)s->grid.nz;
   if (const int st = dalloc(s->d_phasor, n2)) {
     (void)hipGetLastError();
@@ -1553,6 +1579,87 @@ int smcrt_scene_reset_phasor(smcrt_scene* s) {
   const size_t n2 = 2 * (size_t)s->grid.nx * (size_t)s->grid.ny * (size_t)s->grid.nz;
   HIPCHK(hipMemset(s->d_phasor, 0, n2 * sizeof(double)));
   return SMCRT_OK;
+}
+
+// ---- field screens (screen.h, phasor.h screen_hits) -------------------------------------
+int smcrt_scene_set_screens(smcrt_scene* s, const smcrt_screen* screens, int32_t n) {
+  g_last_error.clear();
+  const bool off = !screens || n == 0;
+  std::vector<ScreenDev> plan;
+  int64_t nd = 0;
+  if (!off)  // (before any device call)
+    if (const int st = plan_screens(screens, n, &plan, &nd)) return st;
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  if (const int vst = smcrt::scene_needs_sdf(s, "field screens")) return vst;
+  std::lock_guard<std::mutex> g(s->mu);
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));  // (no launch of this scene may still use the buffer)
+  s->screens.clear();
+  s->screen_doubles = 0;
+  s->d_screens.reset();
+  s->d_screen_field.reset();
+  if (off) return SMCRT_OK;
+  int st = upload(s->d_screens, plan.data(), plan.size(), "screens: table");
+  if (!st) st = dalloc(s->d_screen_field, (size_t)nd);
+  if (st) {
+    (void)hipGetLastError();
+    s->d_screens.reset();
+    s->d_screen_field.reset();
+    return st;
+  }
+  HIPCHK(hipMemset(s->d_screen_field, 0, (size_t)nd * sizeof(double)));
+  s->screens = std::move(plan);
+  s->screen_doubles = nd;
+  return SMCRT_OK;
+}
+
+int smcrt_scene_screen_info(const smcrt_scene* s, int32_t* n, int64_t* n_doubles) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  if (n) *n = (int32_t)s->screens.size();
+  if (n_doubles) *n_doubles = s->screen_doubles;
+  return SMCRT_OK;
+}
+
+int smcrt_scene_read_screens(smcrt_scene* s, double* out) {
+  g_last_error.clear();
+  if (!s || !out) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  if (const int vst = smcrt::scene_needs_sdf(s, "field screens")) return vst;
+  std::lock_guard<std::mutex> g(s->mu);
+  if (s->screens.empty()) return fail(SMCRT_ERR_INVALID_ARG, "no screens are configured on this scene");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  std::vector<double> h((size_t)s->screen_doubles);
+  HIPCHK(hipMemcpy(h.data(), s->d_screen_field, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < h.size(); ++i) out[i] += h[i];
+  return SMCRT_OK;
+}
+
+int smcrt_scene_reset_screens(smcrt_scene* s) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  if (const int vst = smcrt::scene_needs_sdf(s, "field screens")) return vst;
+  std::lock_guard<std::mutex> g(s->mu);
+  if (s->screens.empty()) return fail(SMCRT_ERR_INVALID_ARG, "no screens are configured on this scene");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(hipMemset(s->d_screen_field, 0, (size_t)s->screen_doubles * sizeof(double)));
+  return SMCRT_OK;
+}
+
+int smcrt_screen_hit(const smcrt_screen* screen, const double start[3], const double dir[3], double sep, double* t,
+                     int32_t* pixel) {
+  g_last_error.clear();
+  if (!screen || !start || !dir || !t || !pixel) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  std::vector<ScreenDev> plan;
+  int64_t nd = 0;
+  if (const int st = plan_screens(screen, 1, &plan, &nd)) return st;  // (the statuses are negative)
+  double tt = 0.0;
+  int32_t px = 0;
+  if (!screen_hit(plan[0], v3(start[0], start[1], start[2]), v3(dir[0], dir[1], dir[2]), sep, tt, px)) return 0;
+  *t = tt;
+  *pixel = px;
+  return 1;
 }
 
 int smcrt_normalise_fluence(float* g, const smcrt_grid* grid, uint64_t nphotons) {

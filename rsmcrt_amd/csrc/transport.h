@@ -28,6 +28,7 @@
 #include "srcplan.h"
 #include "cull.h"
 #include "meshcast.h"
+#include "screen.h"
 
 namespace smcrt {
 
@@ -120,6 +121,12 @@ struct KCold {
   const MeshFace* mesh_faces;  // normal and media of each triangle, by the caller's triangle index
   uint32_t mesh_n_nodes;
   uint32_t mesh_ambient;       // the medium of a point from which a cast meets nothing
+  // field screens and the optical-path option (read by the PHAS instantiations of transport_kernel
+  // only, phasor.h; null / 0 otherwise). After the mesh fields, so that those stay where they were.
+  const ScreenDev* screens;    // [n_screens] (screen.h)
+  double* screen_field;        // re, im interleaved; screen i's pixels from screens[i].offset
+  uint32_t n_screens;          // 0: the launch tallies no screens
+  uint32_t phasor_optical;     // != 0: SMCRT_PHASOR_OPTICAL_PATH, a piece adds n * dc to the phase
 };
 
 // watchdog sites (KCold::watchdog bits 0-7; smcrt.hip names them)

@@ -112,6 +112,12 @@ def load_library(path: str = LIB_PATH):
         L.smcrt_scene_set_phasor.argtypes = [C.c_void_p, C.POINTER(abi.PhasorConfig)]
         L.smcrt_scene_read_phasor.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.smcrt_scene_reset_phasor.argtypes = [C.c_void_p]
+        L.smcrt_scene_set_screens.argtypes = [C.c_void_p, C.POINTER(abi.Screen), C.c_int32]
+        L.smcrt_scene_screen_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+        L.smcrt_scene_read_screens.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.smcrt_scene_reset_screens.argtypes = [C.c_void_p]
+        L.smcrt_screen_hit.argtypes = [C.POINTER(abi.Screen), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_int32)]
         L.smcrt_displacement_compile.argtypes = [C.c_char_p, C.POINTER(abi.SdfNode)]
         L.smcrt_displacement_eval.argtypes = [C.POINTER(abi.SdfNode), C.POINTER(C.c_double), C.c_int64,
                                               C.POINTER(C.c_double)]
@@ -367,12 +373,13 @@ class Engine:
                                             vtx.ctypes.data_as(C.POINTER(C.c_double))))
         return hdr, vtx, counts
 
-    def set_phasor(self, wavenumber="sampled"):
+    def set_phasor(self, wavenumber="sampled", optical_path=False):
         """Configure the phasor tally (smcrt_scene_set_phasor): runs made with abi.FLAG_PHASOR then
         add weight * exp(i k phase) to the voxel a photon leaves at every voxel wall it crosses.
         `set_phasor()` takes k = 2 pi / the wavelength each emission samples, `set_phasor(k)` a
         fixed wavenumber (finite, >= 0) for every photon, `set_phasor(None)` turns the tally off
-        and frees the grid."""
+        and frees the grid. With `optical_path` (abi.PHASOR_OPTICAL_PATH) the phase grows by
+        n * length in a layer of refractive index n, for the grid and the field screens alike."""
         L = load_library()
         if wavenumber is None:
             _check(L.smcrt_scene_set_phasor(self._h, None))
@@ -380,6 +387,7 @@ class Engine:
         cfg = abi.PhasorConfig()
         if not (isinstance(wavenumber, str) and wavenumber == "sampled"):
             cfg.fixed_k, cfg.wavenumber = 1, float(wavenumber)
+        cfg.reserved = abi.PHASOR_OPTICAL_PATH if optical_path else 0
         _check(L.smcrt_scene_set_phasor(self._h, C.byref(cfg)))
 
     def phasor(self) -> np.ndarray:
@@ -393,6 +401,40 @@ class Engine:
     def reset_phasor(self):
         """Zero the scene's phasor grid (smcrt_scene_reset_phasor)."""
         _check(load_library().smcrt_scene_reset_phasor(self._h))
+
+    def set_screens(self, screens):
+        """Configure the scene's field screens (smcrt_scene_set_screens): a list of scene.screen(...)
+        rectangles, each recording weight * exp(i k phase) of the photons that cross it, per pixel,
+        in runs made with abi.FLAG_PHASOR (so set_phasor supplies k and the optical-path option).
+        `set_screens(None)` (or an empty list) turns them off and frees the buffer."""
+        L = load_library()
+        screens = list(screens) if screens is not None else []
+        if not screens:
+            _check(L.smcrt_scene_set_screens(self._h, None, 0))
+            self._screen_dims = []
+            return
+        arr = (abi.Screen * len(screens))(*screens)
+        _check(L.smcrt_scene_set_screens(self._h, arr, len(screens)))
+        self._screen_dims = [(int(s.nv), int(s.nu)) for s in screens]
+
+    def screens(self):
+        """The screens' fields (smcrt_scene_read_screens): one complex128 array of shape (nv, nu)
+        per screen, in the order given; they accumulate over runs until reset_screens."""
+        L = load_library()
+        n, nd = C.c_int32(), C.c_int64()
+        _check(L.smcrt_scene_screen_info(self._h, C.byref(n), C.byref(nd)))
+        flat = np.zeros(max(nd.value, 2), dtype=np.float64)
+        _check(L.smcrt_scene_read_screens(self._h, flat.ctypes.data_as(C.POINTER(C.c_double))))
+        out, off = [], 0
+        for nv, nu in getattr(self, "_screen_dims", []):
+            out.append(flat[off:off + 2 * nu * nv].view(np.complex128).reshape(nv, nu).copy())
+            off += 2 * nu * nv
+        assert len(out) == n.value and off == nd.value
+        return out
+
+    def reset_screens(self):
+        """Zero the screens' fields (smcrt_scene_reset_screens)."""
+        _check(load_library().smcrt_scene_reset_screens(self._h))
 
     def invoxel_segments(self) -> int:
         """Deposit segments of the scene's finished launches that the lean path's photon waves

@@ -101,6 +101,20 @@ def write_phasor(fileplace, outfile, phasor, metadata: str | None = None, overwr
                       overwrite=overwrite)
 
 
+def write_screen(fileplace, outfile, field, metadata: str | None = None, overwrite: bool = True) -> str:
+    """abs(field)**2 of one field screen as fp32 to <fileplace>/phasor/<outfile> through write_data,
+    as write_phasor does for the grid, with nz = 1. `field` is one of Engine.screens()'s complex
+    arrays of shape (nv, nu). Returns the file name actually written."""
+    import os
+    f = np.asarray(field)
+    if not np.iscomplexobj(f) or f.ndim != 2:
+        raise ValueError("field must be a complex array of shape (nv, nu)")
+    d = os.path.join(str(fileplace), "phasor")
+    os.makedirs(d, exist_ok=True)
+    return write_data(os.path.join(d, str(outfile)), (np.abs(f) ** 2).astype(np.float32)[None, :, :], metadata,
+                      overwrite=overwrite)
+
+
 def normalise_fluence(jmean, grid: abi.Grid, nphotons: int) -> np.ndarray:
     """normalise_fluence, writer.f90:25-52, on an fp32 copy (the reference's array kind)."""
     a = np.array(jmean, dtype=np.float32, copy=True, order="C")

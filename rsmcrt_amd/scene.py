@@ -743,6 +743,17 @@ def fibre_dect(pos, direction, layer, nbins, focal1=1.0, focal2=1.0, f1_aperture
     return d
 
 
+def screen(origin, eu, ev, nu, nv, sides=0) -> abi.Screen:
+    """A field screen (smcrt_screen): the rectangle origin + u * eu + v * ev, 0 <= u, v < 1, of
+    nu x nv pixels; eu and ev orthogonal. `sides`: 0 records both directions of crossing, +1 only
+    photons going along normalise(eu x ev), -1 only those going against it."""
+    s = abi.Screen()
+    for i in range(3):
+        s.origin[i] = float(origin[i]); s.eu[i] = float(eu[i]); s.ev[i] = float(ev[i])
+    s.nu, s.nv, s.sides, s.reserved = int(nu), int(nv), int(sides), 0
+    return s
+
+
 def det_sizes(dets) -> List[int]:
     return [d.nbins * d.nbins if d.kind == abi.DET_CAMERA else d.nbins for d in dets]
 
