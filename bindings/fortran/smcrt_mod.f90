@@ -28,6 +28,8 @@ module smcrt_mod
     integer(c_int32_t), parameter :: SMCRT_SRC_POINT = 1, SMCRT_SRC_UNIFORM = 2, SMCRT_SRC_PENCIL = 3, &
         SMCRT_SRC_CIRCULAR = 4, SMCRT_SRC_FOCUS = 5, SMCRT_SRC_ANNULUS = 6, SMCRT_SRC_SLM = 7, &
         SMCRT_SRC_DSLIT = 8, SMCRT_SRC_APERTURE = 9
+    ! photons from a per-voxel weight grid (smcrt_scene_set_volume_source); no [source] name maps to it
+    integer(c_int32_t), parameter :: SMCRT_SRC_VOLUME = 10
     ! smcrt_beam_kind (focus_type / annulus_type)
     integer(c_int32_t), parameter :: SMCRT_BEAM_GAUSSIAN = 0, SMCRT_BEAM_SQUARE = 1, SMCRT_BEAM_CIRCLE = 2, &
         SMCRT_BEAM_TOPHAT = 3, SMCRT_BEAM_BESSEL = 4
@@ -270,6 +272,23 @@ module smcrt_mod
             real(c_double), intent(out)     :: t
             integer(c_int32_t), intent(out) :: pixel
         end function smcrt_screen_hit
+
+        ! the volume source (src%kind = SMCRT_SRC_VOLUME): weights(nx*ny*nz), x fastest as jmean, finite
+        ! and >= 0, for instance an excitation run's absorb_f64; c_null_ptr clears the table
+        integer(c_int) function smcrt_scene_set_volume_source(scene, weights) &
+                bind(C, name="smcrt_scene_set_volume_source")
+            import :: c_int, c_ptr
+            type(c_ptr), value :: scene, weights
+        end function smcrt_scene_set_volume_source
+
+        ! voxels with a weight above 0, voxels the pick can return, and the sum of the weights
+        integer(c_int) function smcrt_scene_volume_source_info(scene, n_positive, n_reachable, total) &
+                bind(C, name="smcrt_scene_volume_source_info")
+            import :: c_int, c_int64_t, c_double, c_ptr
+            type(c_ptr), value              :: scene
+            integer(c_int64_t), intent(out) :: n_positive, n_reachable
+            real(c_double), intent(out)     :: total
+        end function smcrt_scene_volume_source_info
 
         integer(c_int) function smcrt_scene_check(scene) bind(C, name="smcrt_scene_check")
             import :: c_int, c_ptr

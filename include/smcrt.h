@@ -142,7 +142,8 @@ typedef enum smcrt_source_kind {
   SMCRT_SRC_ANNULUS = 6,  /* annular beam          photon.f90:850-1043 (2, gaussian 2k+1) */
   SMCRT_SRC_SLM = 7,      /* image source          photon.f90:159-212 (2-D spectrum)     */
   SMCRT_SRC_DSLIT = 8,    /* double slit           photon.f90:712-780 (5 draws)          */
-  SMCRT_SRC_APERTURE = 9  /* square aperture       photon.f90:782-848 (4 draws)          */
+  SMCRT_SRC_APERTURE = 9, /* square aperture       photon.f90:782-848 (4 draws)          */
+  SMCRT_SRC_VOLUME = 10   /* per-voxel weight grid no counterpart: "volume source" below (6 draws) */
 } smcrt_source_kind;
 
 /* Beam profiles: focus_type (photon.f90:394-428) and annulus_type (:878-891). */
@@ -647,6 +648,53 @@ int smcrt_scene_reset_screens(smcrt_scene* scene);
  * 0 for a miss (t and pixel untouched), < 0 for an invalid screen or a NULL argument. */
 int smcrt_screen_hit(const smcrt_screen* screen, const double start[3], const double dir[3], double sep,
                      double* t, int32_t* pixel);
+
+/* ---- volume source (no counterpart in the reference; SDF, voxel and mesh scenes) ---------------
+ * SMCRT_SRC_VOLUME emits photons from inside the grid according to a per-voxel weight: the
+ * fluorescence, Raman or thermal emission that follows an absorb tally. The weights belong to
+ * the scene (smcrt_scene_set_volume_source); of smcrt_source such a run reads `kind` and
+ * `spectrum` only. It always runs the general emitter's kernels, never the lean path.
+ *
+ * Input: w[nx*ny*nz], fp64, in the voxel order of smcrt_tallies.jmean (x fastest), so one run's
+ * absorb_f64 can be passed as it is. Every w[v] is finite and >= 0.
+ * The table, built on the host: cdf[i] = cdf[i-1] + w[i], summed strictly left to right in fp64;
+ * total = cdf[nvox-1] must be finite and > 0; last = the largest i with cdf[i] > cdf[i-1]
+ * (cdf[-1] = 0).
+ * Per emission, with u0 .. u5 the photon's next six draws (then the spectrum's), every operation
+ * in fp64 without fused multiply-add:
+ *   pick   x = u0 * total; i = the smallest index with cdf[i] > x, found by the bisection
+ *          lo = 0, hi = nvox; mid = (lo + hi) / 2; cdf[mid] > x ? hi = mid : lo = mid + 1;
+ *          if there is none, i = last (a guard: a draw is at most 1 - 2^-53, and its product
+ *          with total then stays below total).
+ *          A voxel with cdf[i] == cdf[i-1] is therefore never picked: a zero weight, and a
+ *          weight that vanishes against its prefix (1e-30 after 1e30).
+ *   place  per axis, c the voxel's 0-based cell and face[k] = k * 2 * max / n:
+ *          q = face[c] + u * (face[c+1] - face[c]); pos = q - max; then the emitters' nudge off
+ *          the grid's outer walls (+- 7.9e-7). u1, u2, u3 serve x, y, z.
+ *   dir    the point source's text: phi = u4 * 2 pi, (sin, cos) by the engine's sincos,
+ *          cost = 2 * u5 - 1, sint = sqrt(1 - cost * cost), dir = (sint cos, sint sin, cost).
+ * The photon starts with layer 1 and samples the spectrum as the point source does. The position
+ * always lies in the grid, so no emission is retried.
+ *
+ * smcrt_run and smcrt_run_device accept the kind (SMCRT_ERR_INVALID_ARG naming
+ * smcrt_scene_set_volume_source when the scene holds no table); smcrt_run_origins, the escape
+ * and inverse drivers and smcrt_multi_* answer SMCRT_ERR_UNSUPPORTED. The job/TOML layer never
+ * produces it. */
+
+/* Validate (on the host, before any device call, naming the first offending voxel index: a
+ * non-finite or negative weight, all weights zero, a sum that overflows: SMCRT_ERR_INVALID_ARG),
+ * build the table, upload it and replace any earlier one. weights NULL clears it. */
+int smcrt_scene_set_volume_source(smcrt_scene* scene, const double* weights);
+/* The scene's table: voxels with w > 0, voxels the pick can return (cdf[i] > cdf[i-1]) and the
+ * total (any may be NULL); 0, 0, 0.0 without a table. */
+int smcrt_scene_volume_source_info(const smcrt_scene* scene, int64_t* n_positive, int64_t* n_reachable, double* total);
+/* The rule on the host, the text the kernel runs, with the engine's Philox keyed by photon index
+ * and a constant spectrum: photons first .. first + n - 1 of a run with `seed`. Needs no scene and
+ * no device. pos[3n], dir[3n], voxel[n] (the picked voxel's index in jmean's order); any may be NULL. */
+int smcrt_volume_sample(const double* weights, const smcrt_grid* g, uint64_t seed, uint64_t first, int64_t n,
+                        double* pos, double* dir, int64_t* voxel);
+/* The pick alone for given uniforms u[m] (each in [0, 1)), host only: voxel[m]. */
+int smcrt_volume_pick(const double* weights, int64_t nvox, const double* u, int64_t m, int64_t* voxel);
 
 /* Device-resident variant for multi-GPU and benchmarking: launches on `stream`
  * (a hipStream_t; NULL = the legacy default stream) and accumulates into caller-owned

@@ -36,6 +36,9 @@ OP_UNION, OP_SMOOTH_UNION, OP_SUBTRACTION, OP_INTERSECTION = 0, 1, 2, 3
 # smcrt_source_kind (reference src/photon.f90 emitters)
 SRC_POINT, SRC_UNIFORM, SRC_PENCIL = 1, 2, 3
 SRC_CIRCULAR, SRC_FOCUS, SRC_ANNULUS, SRC_SLM, SRC_DSLIT, SRC_APERTURE = 4, 5, 6, 7, 8, 9
+# no counterpart in the reference: photons from a per-voxel weight grid (Engine.set_volume_source,
+# scene.volume_source); not in SOURCE_KINDS, which names what a job file's [source] may hold
+SRC_VOLUME = 10
 SOURCE_KINDS = {"point": SRC_POINT, "uniform": SRC_UNIFORM, "pencil": SRC_PENCIL, "circular": SRC_CIRCULAR,
                 "focus": SRC_FOCUS, "annulus": SRC_ANNULUS, "slm": SRC_SLM, "dslit": SRC_DSLIT,
                 "aperture": SRC_APERTURE}
@@ -288,6 +291,7 @@ EXPORTED_SYMBOLS = [
     "smcrt_scene_set_phasor", "smcrt_scene_read_phasor", "smcrt_scene_reset_phasor",
     "smcrt_scene_set_screens", "smcrt_scene_screen_info", "smcrt_scene_read_screens", "smcrt_scene_reset_screens",
     "smcrt_screen_hit",
+    "smcrt_scene_set_volume_source", "smcrt_scene_volume_source_info", "smcrt_volume_sample", "smcrt_volume_pick",
     "smcrt_displacement_compile", "smcrt_displacement_eval", "smcrt_displacement_describe",
     "smcrt_voxel_scene_create", "smcrt_scene_deposit_regime",
     "smcrt_mesh_scene_create",

@@ -485,6 +485,8 @@ int smcrt_escape_run(smcrt_scene* scene, const smcrt_source* src, const smcrt_es
   int st = make_sym(cfg, &S);
   if (st) return st;
   if (!scene || !run || !io) return set_error(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  if (src && src->kind == SMCRT_SRC_VOLUME)
+    return set_error(SMCRT_ERR_UNSUPPORTED, "smcrt_escape_run: a volume source has no origin to batch (the escape function's packet is a point source)");
   if (const int vst = smcrt::scene_needs_sdf(scene, "smcrt_escape_run")) return vst;
   if (run->flags & SMCRT_FLAG_TRACK_PATHS)
     return set_error(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");

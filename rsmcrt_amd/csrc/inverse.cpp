@@ -25,6 +25,8 @@ extern "C" {
 int smcrt_inverse_run(smcrt_scene* scene, const smcrt_source* src, const smcrt_inverse_config* cfg,
                       const smcrt_run_config* run, const double* targets, double* steps, smcrt_tallies* io) {
   if (!scene || !src || !cfg || !run || !steps) return set_error(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  if (src->kind == SMCRT_SRC_VOLUME)
+    return set_error(SMCRT_ERR_UNSUPPORTED, "smcrt_inverse_run: a volume source is run by smcrt_run and smcrt_run_device only");
   if (const int vst = smcrt::scene_needs_sdf(scene, "smcrt_inverse_run")) return vst;
   if (cfg->max_steps < 1) return set_error(SMCRT_ERR_INVALID_ARG, "maxNumSteps must be >= 1");
   if (run->flags & SMCRT_FLAG_TRACK_PATHS)

@@ -451,6 +451,8 @@ static void discard_locked(smcrt_multi* m) {
 // tail-bound scene keeps every GPU busy until the end instead of waiting for the slowest of
 // n static shards. Returns when every chunk is launched; nothing is waited for.
 static int accumulate_locked(smcrt_multi* m, const smcrt_source* src, const smcrt_run_config* cfg) {
+  if (src->kind == SMCRT_SRC_VOLUME)  // (the table belongs to one scene: smcrt_scene_set_volume_source)
+    return fail(SMCRT_ERR_UNSUPPORTED, "smcrt_multi_*: a volume source is run by smcrt_run and smcrt_run_device only");
   if (cfg->flags & SMCRT_FLAG_TRACK_PATHS)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
   if (cfg->flags & SMCRT_FLAG_PHASOR)

@@ -668,4 +668,39 @@ int plan_screens(const smcrt_screen* screens, int32_t n, std::vector<ScreenDev>*
   return SMCRT_OK;
 }
 
+int plan_volume_source(const double* w, int64_t nvox, std::vector<double>* cdf, int64_t* last, int64_t* n_positive,
+                       int64_t* n_reachable) {
+  if (!w || !cdf || !last || !n_positive || !n_reachable) return fail(SMCRT_ERR_INVALID_ARG, "volume source: NULL argument");
+  if (nvox < 1 || nvox > 0xFFFFFFFFll)
+    return fail(SMCRT_ERR_INVALID_ARG, "volume source: " + std::to_string(nvox) + " voxels (1 to 2^32 - 1)");
+  for (int64_t i = 0; i < nvox; ++i) {
+    if (!std::isfinite(w[i]))
+      return fail(SMCRT_ERR_INVALID_ARG, "volume source: the weight of voxel " + std::to_string(i) + " is not finite");
+    if (w[i] < 0.0)
+      return fail(SMCRT_ERR_INVALID_ARG, "volume source: the weight of voxel " + std::to_string(i) + " is negative");
+  }
+  cdf->assign((size_t)nvox, 0.0);
+  double run = 0.0;
+  int64_t la = -1, np = 0, nr = 0;
+  for (int64_t i = 0; i < nvox; ++i) {
+    const double next = run + w[i];
+    if (!std::isfinite(next))
+      return fail(SMCRT_ERR_INVALID_ARG, "volume source: the sum of the weights overflows at voxel " + std::to_string(i));
+    if (w[i] > 0.0) ++np;
+    if (next > run) { ++nr; la = i; }
+    run = next;
+    (*cdf)[(size_t)i] = run;
+  }
+  if (la < 0)
+    return fail(SMCRT_ERR_INVALID_ARG, "volume source: every weight is zero (voxel 0 .. " + std::to_string(nvox - 1) + ")");
+  *last = la; *n_positive = np; *n_reachable = nr;
+  return SMCRT_OK;
+}
+
+std::vector<double> grid_faces(const smcrt_grid* grid) {
+  ScenePlan p;
+  plan_faces(grid, p);
+  return p.faces;
+}
+
 }  // namespace smcrt

@@ -201,6 +201,19 @@ inline size_t mesh_lds(const ScenePlan& p, uint32_t dep_words) { return voxel_ld
 // convention as plan_scene.
 int plan_screens(const smcrt_screen* screens, int32_t n, std::vector<ScreenDev>* out, int64_t* n_doubles);
 
+// The volume source's table (smcrt_scene_set_volume_source, smcrt_volume_sample, smcrt_volume_pick;
+// the rule reads it in volsrc.h): validates w[nvox] (1 <= nvox < 2^32; every weight finite and
+// >= 0; not all zero; no running sum overflows), naming the first offending voxel index, and fills
+// cdf[i] = cdf[i-1] + w[i], summed left to right. *last is the largest i with cdf[i] > cdf[i-1],
+// *n_positive counts w[i] > 0 and *n_reachable cdf[i] > cdf[i-1]. Same return convention as
+// plan_scene.
+int plan_volume_source(const double* w, int64_t nvox, std::vector<double>* cdf, int64_t* last, int64_t* n_positive,
+                       int64_t* n_reachable);
+
+// The faces every scene of this grid has (ScenePlan::faces: x (nx+1) | y (ny+1) | z (nz+2)), for
+// the scene-free smcrt_volume_sample.
+std::vector<double> grid_faces(const smcrt_grid* grid);
+
 // ---- pure rules of the launch path ----
 // the lean path's dynamic LDS (ws_kernel): staged props + faces, then the block's bucket words
 inline size_t lean_lds(const ScenePlan& p) {

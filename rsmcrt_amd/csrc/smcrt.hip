@@ -30,6 +30,7 @@
 #include "deposit.h"
 #include "devmem.h"
 #include "hosterr.h"
+#include "hostrng.h"
 #include "sceneplan.h"
 
 using namespace smcrt;
@@ -195,6 +196,11 @@ struct smcrt_scene : ScenePlan {
   DevBuf<ScreenDev> d_screens;
   DevBuf<double> d_screen_field;
   int grid_blocks_phas_scr[2] = {0, 0};
+  // the volume source (smcrt_scene_set_volume_source; volsrc.h): the running sums of the weights
+  // and what the pick and smcrt_scene_volume_source_info read; d_vs_cdf null: no table
+  DevBuf<double> d_vs_cdf;
+  int64_t vs_last = 0, vs_positive = 0, vs_reachable = 0;
+  double vs_total = 0.0;
   std::mutex mu;
 };
 
@@ -939,6 +945,15 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.screen_field = scr ? (double*)s->d_screen_field : nullptr;
   Ch.n_screens = scr ? (uint32_t)s->screens.size() : 0u;
   Ch.phasor_optical = phas && (s->phasor_cfg.reserved & SMCRT_PHASOR_OPTICAL_PATH) ? 1u : 0u;
+  // the volume source's table (emit_ext reads it for SMCRT_SRC_VOLUME only; launch() has checked it)
+  const bool vsrc = src->kind == SMCRT_SRC_VOLUME && s->d_vs_cdf;
+  Ch.vs_cdf = vsrc ? (const double*)s->d_vs_cdf : nullptr;
+  Ch.vs_xface = vsrc ? K.xface : nullptr;
+  Ch.vs_yface = vsrc ? K.yface : nullptr;
+  Ch.vs_zface = vsrc ? K.zface : nullptr;
+  Ch.vs_total = vsrc ? s->vs_total : 0.0;
+  Ch.vs_nvox = vsrc ? (uint32_t)((int64_t)s->grid.nx * s->grid.ny * s->grid.nz) : 0u;
+  Ch.vs_last = vsrc ? (uint32_t)s->vs_last : 0u;
   Ch.vox_labels = s->d_labels;
   Ch.vox_n_media = s->voxel ? (uint32_t)s->n_top : 0u;
   Ch.vox_reserved = 0;
@@ -971,7 +986,12 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
 
 static int launch(smcrt_scene* s, const smcrt_source* src, const smcrt_run_config* cfg,
                   const smcrt_device_tallies& dt, hipStream_t stream, const OriginRun* orun = nullptr) {
-  if (src->kind < SMCRT_SRC_POINT || src->kind > SMCRT_SRC_APERTURE) return fail(SMCRT_ERR_INVALID_ARG, "bad source kind");
+  if (src->kind < SMCRT_SRC_POINT || src->kind > SMCRT_SRC_VOLUME) return fail(SMCRT_ERR_INVALID_ARG, "bad source kind");
+  if (src->kind == SMCRT_SRC_VOLUME) {
+    if (orun) return fail(SMCRT_ERR_UNSUPPORTED, "smcrt_run_origins: a volume source has no origin to batch");
+    if (!s->d_vs_cdf)
+      return fail(SMCRT_ERR_INVALID_ARG, "a volume source needs smcrt_scene_set_volume_source first (the scene holds no table)");
+  }
   if (cfg->n_photons == 0) return SMCRT_OK;
   // sources other than point/uniform/pencil, a sampled spectrum or batched origins: the
   // general emitter
@@ -1202,6 +1222,8 @@ int smcrt_run_origins(smcrt_scene* s, const smcrt_source* src, const double* ori
                       const smcrt_run_config* cfg, double* det_totals, smcrt_tallies* io) {
   g_last_error.clear();
   if (!s || !cfg || !io || (n_origins > 0 && !origins)) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  if (src && src->kind == SMCRT_SRC_VOLUME)
+    return fail(SMCRT_ERR_UNSUPPORTED, "smcrt_run_origins: a volume source has no origin to batch (the batch is a point source)");
   if (const int vst = smcrt::scene_needs_sdf(s, "smcrt_run_origins")) return vst;
   if (n_origins < 0) return fail(SMCRT_ERR_INVALID_ARG, "n_origins < 0");
   if (cfg->flags & SMCRT_FLAG_TRACK_PATHS)
@@ -1660,6 +1682,100 @@ int smcrt_screen_hit(const smcrt_screen* screen, const double start[3], const do
   *t = tt;
   *pixel = px;
   return 1;
+}
+
+// ---- the volume source (volsrc.h, emit_ext case SMCRT_SRC_VOLUME) -------------------------
+int smcrt_scene_set_volume_source(smcrt_scene* s, const double* weights) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  std::vector<double> cdf;
+  int64_t last = 0, np = 0, nr = 0;
+  if (weights)  // (before any device call)
+    if (const int st = plan_volume_source(weights, (int64_t)s->grid.nx * s->grid.ny * s->grid.nz, &cdf, &last, &np, &nr))
+      return st;
+  std::lock_guard<std::mutex> g(s->mu);
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));  // (no launch of this scene may still read the table)
+  for (int i = 0; i < MAX_SLOTS; ++i)
+    if (s->lpending[i]) HIPCHK(hipEventSynchronize(s->lev[i]));
+  s->d_vs_cdf.reset();
+  s->vs_last = s->vs_positive = s->vs_reachable = 0;
+  s->vs_total = 0.0;
+  if (!weights) return SMCRT_OK;
+  if (const int st = upload(s->d_vs_cdf, cdf.data(), cdf.size(), "volume source: table")) {
+    (void)hipGetLastError();
+    s->d_vs_cdf.reset();
+    return st;
+  }
+  s->vs_last = last; s->vs_positive = np; s->vs_reachable = nr;
+  s->vs_total = cdf.back();
+  return SMCRT_OK;
+}
+
+int smcrt_scene_volume_source_info(const smcrt_scene* s, int64_t* n_positive, int64_t* n_reachable, double* total) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  if (n_positive) *n_positive = s->vs_positive;
+  if (n_reachable) *n_reachable = s->vs_reachable;
+  if (total) *total = s->vs_total;
+  return SMCRT_OK;
+}
+
+int smcrt_volume_pick(const double* weights, int64_t nvox, const double* u, int64_t m, int64_t* voxel) {
+  g_last_error.clear();
+  if (!weights || m < 0 || (m > 0 && (!u || !voxel))) return fail(SMCRT_ERR_INVALID_ARG, "volume pick: bad arguments");
+  std::vector<double> cdf;
+  int64_t last = 0, np = 0, nr = 0;
+  if (const int st = plan_volume_source(weights, nvox, &cdf, &last, &np, &nr)) return st;
+  for (int64_t i = 0; i < m; ++i) {
+    if (!(u[i] >= 0.0 && u[i] < 1.0))
+      return fail(SMCRT_ERR_INVALID_ARG, "volume pick: uniform " + std::to_string(i) + " is not in [0, 1)");
+    voxel[i] = (int64_t)volsrc_pick(cdf.data(), (uint32_t)nvox, (uint32_t)last, cdf.back(), u[i]);
+  }
+  return SMCRT_OK;
+}
+
+int smcrt_volume_sample(const double* weights, const smcrt_grid* g, uint64_t seed, uint64_t first, int64_t n, double* pos,
+                        double* dir, int64_t* voxel) {
+  g_last_error.clear();
+  if (!weights || !g || n < 0) return fail(SMCRT_ERR_INVALID_ARG, "volume sample: bad arguments");
+  if (g->nx < 1 || g->ny < 1 || g->nz < 1 || !(g->xmax > 0.0) || !(g->ymax > 0.0) || !(g->zmax > 0.0) ||
+      !std::isfinite(g->xmax) || !std::isfinite(g->ymax) || !std::isfinite(g->zmax))
+    return fail(SMCRT_ERR_INVALID_ARG, "volume sample: bad grid");
+  const int64_t nvox = (int64_t)g->nx * g->ny * g->nz;
+  std::vector<double> cdf;
+  int64_t last = 0, np = 0, nr = 0;
+  if (const int st = plan_volume_source(weights, nvox, &cdf, &last, &np, &nr)) return st;
+  const std::vector<double> faces = grid_faces(g);  // (as every scene has them)
+  const double* xf = faces.data();
+  const double* yf = xf + (g->nx + 1);
+  const double* zf = yf + (g->ny + 1);
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int64_t i = 0; i < n; ++i) {
+    // the photon's stream (detmath.h Rng): draw d is the (d & 1) half of block (d >> 1, 0, pid_lo, pid_hi)
+    const uint64_t pid = first + (uint64_t)i;
+    double u[6];
+    for (uint32_t b = 0; b < 3; ++b) {
+      uint32_t c[4] = {b, 0u, (uint32_t)pid, (uint32_t)(pid >> 32)};
+      host_philox(c, k0, k1);
+      u[2 * b] = (double)((((uint64_t)c[1] << 32) | c[0]) >> 11) * 0x1.0p-53;
+      u[2 * b + 1] = (double)((((uint64_t)c[3] << 32) | c[2]) >> 11) * 0x1.0p-53;
+    }
+    const uint32_t v = volsrc_pick(cdf.data(), (uint32_t)nvox, (uint32_t)last, cdf.back(), u[0]);
+    const uint32_t ci = v % (uint32_t)g->nx, cj = (v / (uint32_t)g->nx) % (uint32_t)g->ny,
+                   ck = v / ((uint32_t)g->nx * (uint32_t)g->ny);
+    if (voxel) voxel[i] = (int64_t)v;
+    if (pos) {
+      pos[3 * i] = volsrc_place(xf[ci], xf[ci + 1], u[1], g->xmax);
+      pos[3 * i + 1] = volsrc_place(yf[cj], yf[cj + 1], u[2], g->ymax);
+      pos[3 * i + 2] = volsrc_place(zf[ck], zf[ck + 1], u[3], g->zmax);
+    }
+    if (dir) {
+      const V3 d = volsrc_dir(u[4], u[5]);
+      dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z;
+    }
+  }
+  return SMCRT_OK;
 }
 
 int smcrt_normalise_fluence(float* g, const smcrt_grid* grid, uint64_t nphotons) {

@@ -122,7 +122,7 @@ int build_src_plan(const smcrt_source* s, const smcrt_grid* g, SrcPlan* p, std::
     R = t;
     if (flip && !mat::veq(a, b)) t.m[2][2] = 1.0;
     T = mat::matmul(t, mat::invert(mat::translate(start.x, start.y, start.z)));
-  } else if (s->kind < SMCRT_SRC_POINT || s->kind > SMCRT_SRC_APERTURE) {
+  } else if (s->kind < SMCRT_SRC_POINT || s->kind > SMCRT_SRC_VOLUME) {  // (volume: only the spectrum below)
     *err = "bad source kind";
     return SMCRT_ERR_INVALID_ARG;
   }

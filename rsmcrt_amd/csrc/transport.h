@@ -29,6 +29,7 @@
 #include "cull.h"
 #include "meshcast.h"
 #include "screen.h"
+#include "volsrc.h"
 
 namespace smcrt {
 
@@ -127,6 +128,15 @@ struct KCold {
   double* screen_field;        // re, im interleaved; screen i's pixels from screens[i].offset
   uint32_t n_screens;          // 0: the launch tallies no screens
   uint32_t phasor_optical;     // != 0: SMCRT_PHASOR_OPTICAL_PATH, a piece adds n * dc to the phase
+  // the volume source (read by emit_ext's case SMCRT_SRC_VOLUME only, volsrc.h; null / 0 otherwise).
+  // After the screen fields, so that those stay where they were.
+  const double* vs_cdf;        // [vs_nvox] running sums of the weights, voxel order as jmean
+  const double* vs_xface;      // the scene's faces in device memory (the kernels' own K.xface may
+  const double* vs_yface;      // point into LDS, or be unused in the power-of-two grid mode)
+  const double* vs_zface;
+  double vs_total;             // cdf[vs_nvox - 1]
+  uint32_t vs_nvox;            // nx * ny * nz
+  uint32_t vs_last;            // the largest i with cdf[i] > cdf[i-1]
 };
 
 // watchdog sites (KCold::watchdog bits 0-7; smcrt.hip names them)
@@ -612,7 +622,9 @@ constexpr int MAX_RANG_TRIES = 1000;  // rang's rejection loop (random_mod.f90:1
 // wavelength (photon%fact; slm has no wavelength to sample and keeps the reference's 500e-9,
 // photon.f90:202-204).
 template <class PH = NoPhasLane>
-__device__ __forceinline__ void emit_ext(const KParams& K, const SrcPlan& P, Lane& L, uint32_t oidx, PH* ph = nullptr) {
+__device__ __forceinline__ void emit_ext(const KParams& K, const KCold* __restrict__ C, Lane& L, uint32_t oidx,
+                                         PH* ph = nullptr) {
+  const SrcPlan& P = C->plan;
   const double TWOPI = 6.283185307179586;
   double wl, tmp;
   if constexpr (!std::is_empty_v<PH>) ph->phase = 0.0;
@@ -725,6 +737,24 @@ __device__ __forceinline__ void emit_ext(const KParams& K, const SrcPlan& P, Lan
       if constexpr (!std::is_empty_v<PH>) wl = 500.e-9;
       break;
     }
+    case SMCRT_SRC_VOLUME: {  // no counterpart in photon.f90: volsrc.h (draws u0 .. u5, then the spectrum's)
+      const double u0 = L.rng.next(K.key0, K.key1);
+      const uint32_t v = volsrc_pick(C->vs_cdf, C->vs_nvox, C->vs_last, C->vs_total, u0);
+      const uint32_t ci = v % (uint32_t)K.nx, cj = (v / (uint32_t)K.nx) % (uint32_t)K.ny,
+                     ck = v / ((uint32_t)K.nx * (uint32_t)K.ny);
+      const double* __restrict__ fx = C->vs_xface + ci;
+      const double* __restrict__ fy = C->vs_yface + cj;
+      const double* __restrict__ fz = C->vs_zface + ck;
+      const double px = volsrc_place(fx[0], fx[1], L.rng.next(K.key0, K.key1), K.xmax);
+      const double py = volsrc_place(fy[0], fy[1], L.rng.next(K.key0, K.key1), K.ymax);
+      const double pz = volsrc_place(fz[0], fz[1], L.rng.next(K.key0, K.key1), K.zmax);
+      L.pos = v3(px, py, pz);
+      const double u4 = L.rng.next(K.key0, K.key1);
+      L.dir = volsrc_dir(u4, L.rng.next(K.key0, K.key1));
+      L.layer = 1;
+      spec_sample(K, P, L, wl, tmp);
+      break;
+    }
     default: {  // dslit :712-780, aperture :782-848
       spec_sample(K, P, L, wl, tmp);
       double x1, y1, z1, x2, y2, z2;
@@ -774,7 +804,7 @@ __device__ __forceinline__ void emit(const KParams& K, const KCold* __restrict__
     ph->k = C->phasor_k;
   }
   if constexpr (XSRC) {
-    emit_ext(K, C->plan, L, oidx, ph);
+    emit_ext(K, C, L, oidx, ph);
     if constexpr (!std::is_empty_v<PH>) {
       if (C->phasor_fixed) ph->k = C->phasor_k;
     }

@@ -118,6 +118,13 @@ def load_library(path: str = LIB_PATH):
         L.smcrt_scene_reset_screens.argtypes = [C.c_void_p]
         L.smcrt_screen_hit.argtypes = [C.POINTER(abi.Screen), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                        C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+        L.smcrt_scene_set_volume_source.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.smcrt_scene_volume_source_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                     C.POINTER(C.c_double)]
+        L.smcrt_volume_sample.argtypes = [C.POINTER(C.c_double), C.POINTER(abi.Grid), C.c_uint64, C.c_uint64, C.c_int64,
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        L.smcrt_volume_pick.argtypes = [C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.c_int64,
+                                        C.POINTER(C.c_int64)]
         L.smcrt_displacement_compile.argtypes = [C.c_char_p, C.POINTER(abi.SdfNode)]
         L.smcrt_displacement_eval.argtypes = [C.POINTER(abi.SdfNode), C.POINTER(C.c_double), C.c_int64,
                                               C.POINTER(C.c_double)]
@@ -435,6 +442,31 @@ class Engine:
     def reset_screens(self):
         """Zero the screens' fields (smcrt_scene_reset_screens)."""
         _check(load_library().smcrt_scene_reset_screens(self._h))
+
+    def set_volume_source(self, weights):
+        """Give the scene the weights of the volume source (smcrt_scene_set_volume_source): a flat
+        array of nx * ny * nz values, x fastest, or one of shape (nz, ny, nx) as Result's grids are,
+        finite and >= 0, for instance an excitation run's absorb_f64. Runs with scene.volume_source()
+        then emit from voxel v with probability weights[v] / sum. A second call replaces the table,
+        `set_volume_source(None)` clears it."""
+        L = load_library()
+        if weights is None:
+            _check(L.smcrt_scene_set_volume_source(self._h, None))
+            return
+        g = self.grid
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != (g.nz * g.ny * g.nx,) and w.shape != (g.nz, g.ny, g.nx):
+            raise ValueError(f"weights of shape {w.shape}: expected ({g.nz * g.ny * g.nx},) or ({g.nz}, {g.ny}, {g.nx})")
+        w = np.ascontiguousarray(w).reshape(-1)
+        _check(L.smcrt_scene_set_volume_source(self._h, w.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def volume_source_info(self) -> dict:
+        """The scene's volume-source table (smcrt_scene_volume_source_info): n_positive (weights
+        above 0), n_reachable (voxels the pick can return: a weight that vanishes against the sum
+        before it is never picked) and total; all 0 without a table."""
+        a, b, t = C.c_int64(), C.c_int64(), C.c_double()
+        _check(load_library().smcrt_scene_volume_source_info(self._h, C.byref(a), C.byref(b), C.byref(t)))
+        return {"n_positive": a.value, "n_reachable": b.value, "total": t.value}
 
     def invoxel_segments(self) -> int:
         """Deposit segments of the scene's finished launches that the lean path's photon waves

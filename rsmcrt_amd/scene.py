@@ -615,6 +615,16 @@ def aperture_source() -> abi.Source:
     return _src(abi.SRC_APERTURE)
 
 
+def volume_source(spectrum=None) -> abi.Source:
+    """The volume source (abi.SRC_VOLUME; no counterpart in photon.f90): photons start inside the
+    grid, in voxels picked in proportion to the weights the engine holds (Engine.set_volume_source),
+    uniformly within the voxel, in an isotropic direction. Of the source only `spectrum` is read."""
+    s = _src(abi.SRC_VOLUME)
+    if spectrum is not None:
+        attach_spectrum(s, spectrum)
+    return s
+
+
 def spectrum_constant(wavelength=500.0) -> abi.Spectrum:
     sp = abi.Spectrum()
     sp.kind, sp.wavelength = abi.SPEC_CONSTANT, float(wavelength)
