@@ -1,0 +1,327 @@
+"""Test infrastructure only: the scenes of DESIGN.md §3.5 in their three forms (SDF, voxel, mesh),
+their closed-form expectations (tests/analytic_ref.py) and the statistics that compare a run with
+them. Shared by tests/test_analytic_cpu.py and tests/test_gpu_analytic.py; imports neither the
+engine nor the restatements, so that what is compared with what stays in the tests.
+
+The grid has three different voxel edges (0.25, 0.125, 0.24) and three different counts, so a
+swapped axis or stride cannot pass; the slab's planes z = +-0.48 are voxel faces.
+"""
+from __future__ import annotations
+
+import functools
+import math
+
+import numpy as np
+from scipy import stats
+
+from rsmcrt_amd import builders, scene
+from tests import analytic_ref as AR
+
+NX, NY, NZ = 8, 12, 10
+HALF = (1.0, 0.75, 1.2)
+EDGES = tuple(2.0 * h / n for h, n in zip(HALF, (NX, NY, NZ)))
+DIAG = math.sqrt(sum(e * e for e in EDGES))  # no photon leaves more track than this in one crossing
+Z_HALF = 0.48                                # faces 3 and 7 of the 11 z faces
+K_SLAB = slice(3, 7)
+# A mesh scene takes no step off a surface it has crossed (DESIGN.md §7 "Mesh media"): a leg that
+# starts on a surface lying in a voxel wall finds its position and its cell on different sides of
+# that wall, which is the reference's error stop (a counted fault), for every photon. The mesh
+# form's planes therefore lie 1e-6 inside the walls, and its reference is computed for them. In
+# scene C that leaves 1e-6 / 0.24 of the two voxel layers next to a plane in the other medium.
+MESH_INSET = 1e-6
+N_VOXELS = NX * NY * NZ
+SEED = 123456789
+BATCHES = 24
+ALPHA = 1e-3   # family-wise false-alarm rate of one test, shared equally by its statistics
+MIN_EVENTS = 100.0
+FORMS = ("sdf", "voxel", "mesh")
+
+# scene A
+A_MU = 2.0
+A_SRC = (0.09, -0.05, 0.10)
+# scene B
+B_N_IN, B_MU = 1.5, 2.0
+B_ORIGIN = (-0.62, 0.13, 0.93)
+B_DIR = (0.5, 0.2, -0.84)
+B_POOL_CAP = 1e-3
+# The engine moves a photon 1e-8 past every voxel wall and 2e-8 past every surface it crosses
+# (update_pos, tauint2), so a track can be short by a few 1e-8 / |direction component| per voxel.
+# Where every photon deposits the same chord the batch variance is zero and this is all there is:
+# 1e-6 per photon and voxel bounds it (three walls, components above 0.1) and is added to the
+# standard error of scene B's tracks. In those voxels it is the whole denominator: an absolute
+# tolerance of 1e-6 per photon (1e-5 of the track), not a t test. In the stochastic voxels the
+# standard error is about ten times larger at 2e7 photons.
+B_TRACK_SLOP = 1e-6
+# scene C
+C_IN = (6.0, 0.8, 0.7, 1.4)    # mus, mua, g, n of the slab
+C_OUT = (2.5, 0.4, 0.3, 1.0)
+C_SRC = (0.09, -0.05, 0.10)
+C_POOL_CAP = 0.05
+
+
+def grid():
+    return scene.grid(NX, NY, NZ, *HALF)
+
+
+def faces():
+    return AR.faces(NX, HALF[0]), AR.faces(NY, HALF[1]), AR.faces(NZ, HALF[2])
+
+
+def z_half(form):
+    return Z_HALF - MESH_INSET if form == "mesh" else Z_HALF
+
+
+# ------------------------------------------------------------------------------ scenes ----
+def _layered(form, inner, outer):
+    """A slab |z| < Z_HALF of `inner` in `outer`, both wider than the grid."""
+    if form == "sdf":
+        return scene.Scene([scene.box((20.0, 20.0, 2.0 * Z_HALF), inner, 1), scene.box((40.0, 40.0, 40.0), outer, 2)])
+    if form == "voxel":
+        lab = np.zeros((NX, NY, NZ), dtype=np.uint8)
+        lab[:, :, K_SLAB] = 1
+        return scene.VoxelScene(lab, [outer, inner])
+    ms = scene.MeshScene([inner, outer], ambient=1)
+    zh = z_half("mesh")
+    return ms.add_surface(*builders.box_mesh((-10.0, -10.0, -zh), (10.0, 10.0, zh)), 0, 1)
+
+
+def scene_a(form):
+    """(scene, source): a homogeneous absorber, mus = 0 and mua = A_MU, around a point source."""
+    m = scene.mono(0.0, A_MU, 0.0, 1.0)
+    src = scene.point_source(A_SRC)
+    if form == "sdf":
+        return scene.Scene([scene.box((20.0, 20.0, 20.0), m, 1)]), src
+    if form == "voxel":
+        return scene.VoxelScene(np.zeros((NX, NY, NZ), dtype=np.uint8), [m]), src
+    ms = scene.MeshScene([m, m], ambient=1)  # one box far beyond the grid; the same medium around it
+    return ms.add_surface(*builders.box_mesh((-10.0, -10.0, -10.0), (10.0, 10.0, 10.0)), 0, 1), src
+
+
+def scene_b(form):
+    """(scene, source): an oblique pencil beam through an absorbing slab of n = 1.5 in vacuum."""
+    d = np.array(B_DIR) / math.sqrt(sum(c * c for c in B_DIR))
+    return (_layered(form, scene.mono(0.0, B_MU, 0.0, B_N_IN), scene.mono(0.0, 0.0, 0.0, 1.0)),
+            scene.pencil_source(B_ORIGIN, tuple(d)))
+
+
+def scene_c(form):
+    """(scene, source): B's layers with scattering in both media, a point source inside the slab."""
+    return _layered(form, scene.mono(*C_IN), scene.mono(*C_OUT)), scene.point_source(C_SRC)
+
+
+def mua_c():
+    """mua of every voxel of scene C, (nz, ny, nx)."""
+    m = np.full((NZ, NY, NX), C_OUT[1])
+    m[K_SLAB] = C_IN[1]
+    return m
+
+
+# -------------------------------------------------------------------------- references ----
+def swapped(a, axes):
+    """The grid `a` stored with two axes exchanged ("xy", "xz" or "yz") and read as (nz, ny, nx):
+    what a swapped stride does. For the negative controls only."""
+    order = {"xy": (0, 2, 1), "xz": (2, 1, 0), "yz": (1, 0, 2)}[axes]
+    return np.ascontiguousarray(a.transpose(order)).reshape(NZ, NY, NX)
+
+
+@functools.lru_cache(maxsize=None)
+def reference_a(mu=A_MU, src=A_SRC, swap=None):
+    """(T, p): expected track and absorption probability per photon and voxel. mu, src and swap
+    (two axes exchanged, see `swapped`) are varied only by the negative controls."""
+    t = AR.point_source_track(*faces(), src, mu)
+    if swap:
+        t = swapped(t, swap)
+    return t, mu * t
+
+
+@functools.lru_cache(maxsize=None)
+def reference_b(form="sdf", n_in=B_N_IN, polarisation="unpolarised", mu=B_MU, origin=B_ORIGIN, swap=None):
+    """(T, p) of scene B in `form`; the other arguments are varied only by the negative controls."""
+    t, p = AR.beam_slab(*faces(), origin, B_DIR, z_half(form), n_in, mu, polarisation=polarisation)
+    if swap:
+        t, p = swapped(t, swap), swapped(p, swap)
+    return t, p
+
+
+# -------------------------------------------------------------------------- statistics ----
+def run_batches(run, n_batch, batches=BATCHES):
+    """`run(first_photon, n)` -> Result for each of `batches` disjoint photon ranges of one seed:
+    (jmean per batch [B, nz, ny, nx], absorb per batch, summed counters as a dict)."""
+    jm, ab, ctr = [], [], {}
+    for b in range(batches):
+        r = run(b * n_batch, n_batch)
+        jm.append(r.jmean.copy())
+        ab.append(r.absorb.copy())
+        for k, v in r.counters_dict().items():
+            ctr[k] = ctr.get(k, 0) + v
+    return np.array(jm), np.array(ab), ctr
+
+
+def _bins(expected_events):
+    """Every entry with at least MIN_EVENTS expected events is a bin of its own; those with fewer
+    (and more than none) are summed into one pooled bin. Returns (index arrays of the bins, the
+    pooled index array or None)."""
+    e = expected_events.ravel()
+    own = np.flatnonzero(e >= MIN_EVENTS)
+    pooled = np.flatnonzero((e > 0.0) & (e < MIN_EVENTS))
+    return own, (pooled if pooled.size else None)
+
+
+def count_stats(counts, p, n, alpha):
+    """Multinomial counts against probabilities p: each photon falls into at most one voxel, so a
+    bin holds Binomial(n, p_v): z_v = (count - n p_v) / sqrt(n p_v (1 - p_v)). Returns a dict with
+    max|z|, sum z^2, the number of bins V, the pooled share of the expectation and the bounds:
+    `alpha` is shared by two statistics: max|z| over V bins must stay below the two-sided normal
+    quantile at alpha / (2 * 2 V) each, and sum z^2 inside the chi^2_V quantiles at alpha / 4 on
+    either side (p_v << 1 makes the bins independent to that order)."""
+    c, q = np.asarray(counts, dtype=np.float64).ravel(), np.asarray(p, dtype=np.float64).ravel()
+    own, pooled = _bins(n * q)
+    cc, qq = c[own], q[own]
+    if pooled is not None:
+        cc, qq = np.append(cc, c[pooled].sum()), np.append(qq, q[pooled].sum())
+    z = (cc - n * qq) / np.sqrt(n * qq * (1.0 - qq))
+    v = len(z)
+    a = alpha / 2.0
+    return {"max_z": float(np.abs(z).max()), "chi2": float((z * z).sum()), "bins": v,
+            "n_pooled": 0 if pooled is None else int(pooled.size),
+            "pooled_share": 0.0 if pooled is None else float(q[pooled].sum() / q.sum()),
+            "z_bound": float(stats.norm.isf(a / (2.0 * v))),
+            "chi2_lo": float(stats.chi2.ppf(a / 2.0, v)), "chi2_hi": float(stats.chi2.isf(a / 2.0, v))}
+
+
+def binomial_z(count, p, n):
+    """z of a Binomial(n, p) count; |z| is held below binomial_bound(alpha)."""
+    return (count - n * p) / math.sqrt(n * p * (1.0 - p))
+
+
+def binomial_bound(alpha):
+    return float(stats.norm.isf(alpha / 2.0))
+
+
+MEAN_T2_DRAWS = 1_000_000
+MEAN_T2_NORMAL_BINS = 200
+
+
+@functools.lru_cache(maxsize=None)
+def mean_t2_bounds(v, nu, a_side):
+    """The quantiles at a_side and 1 - a_side of the mean of v independent squares of Student-t
+    variables with nu degrees of freedom. From MEAN_T2_NORMAL_BINS bins on: normal, with mean
+    nu / (nu - 2) and variance 2 nu^2 (nu - 1) / ((nu - 2)^2 (nu - 4) v), the moments of F(1, nu).
+    Below (scene B's few dozen bins, where the heavy tail of t^2 makes a normal quantile far too
+    small): the empirical quantiles of MEAN_T2_DRAWS draws from a fixed seed."""
+    if v >= MEAN_T2_NORMAL_BINS:
+        m = nu / (nu - 2.0)
+        sd = math.sqrt(2.0 * nu * nu * (nu - 1.0) / ((nu - 2.0) ** 2 * (nu - 4.0) * v))
+        z = float(stats.norm.isf(a_side))
+        return m - z * sd, m + z * sd
+    rng = np.random.default_rng(1234567)
+    chunk = 100_000
+    means = np.concatenate([(rng.standard_t(nu, size=(chunk, v)) ** 2).mean(axis=1)
+                            for _ in range(MEAN_T2_DRAWS // chunk)])
+    return float(np.quantile(means, a_side)), float(np.quantile(means, 1.0 - a_side))
+
+
+def batch_stats(samples, expected, events, alpha, slop=0.0):
+    """Batch means against an expectation: samples [B, ...] per batch, expected [...] per batch,
+    events [...] the expected number of contributing photons over all batches (the pooling rule of
+    count_stats). t_v = (mean_v - expected_v) / sqrt(s_v^2 / B + slop^2) is Student-t with B - 1
+    degrees of freedom when slop = 0 (slop: a bound on a systematic error per bin, which the sum
+    takes once per bin). The grid's sum is one more statistic. `alpha` is shared by four
+    statistics: max|t| over V bins below the two-sided t quantile at alpha / (4 * 2 V); the mean of
+    t_v^2 inside the quantiles, at alpha / 8 on either side, of the mean of V independent squares
+    of Student-t variables (mean_t2_bounds: too small a value, an overestimated variance, fails as
+    too large a one does; photons shared by the voxels on one ray correlate the bins, which widens
+    the true spread, so the bounds err to the strict side); as an extra check each t_v mapped to
+    the chi^2_1 value of the same tail probability, q_v = chi2_1.isf(2 t_nu.sf(|t_v|)), whose sum
+    is chi^2_V and must stay below its quantile at alpha / 4; and |t| of the sum below the t
+    quantile at alpha / (4 * 2). "pooled_share" is the pooled bins' share of the expectation."""
+    s = np.asarray(samples, dtype=np.float64).reshape(len(samples), -1)
+    e = np.asarray(expected, dtype=np.float64).ravel()
+    own, pooled = _bins(np.asarray(events, dtype=np.float64))
+    x, m = s[:, own], e[own]
+    if pooled is not None:
+        x, m = np.hstack([x, s[:, pooled].sum(axis=1, keepdims=True)]), np.append(m, e[pooled].sum())
+    b = x.shape[0]
+    nu = b - 1
+
+    def tstat(col, want, tol):
+        return (col.mean(axis=0) - want) / np.sqrt(col.var(axis=0, ddof=1) / b + tol * tol)
+
+    t = tstat(x, m, slop)
+    used = np.concatenate([own, pooled]) if pooled is not None else own
+    t_sum = float(tstat(s[:, used].sum(axis=1), e[used].sum(), slop * len(used)))
+    v = len(t)
+    a = alpha / 4.0
+    q = stats.chi2.isf(2.0 * stats.t.sf(np.abs(t), nu), 1)
+    lo, hi = mean_t2_bounds(v, nu, a / 2.0)
+    total = float(e.sum())
+    return {"max_t": float(np.abs(t).max()), "mean_t2": float((t * t).mean()), "score": float(q.sum()),
+            "t_sum": t_sum, "bins": v, "n_pooled": 0 if pooled is None else int(pooled.size),
+            "pooled_share": float(e[pooled].sum() / total) if pooled is not None and total > 0.0 else 0.0,
+            "t_bound": float(stats.t.isf(a / (2.0 * v), nu)), "mean_t2_lo": lo, "mean_t2_hi": hi,
+            "score_bound": float(stats.chi2.isf(a, v)), "t_sum_bound": float(stats.t.isf(a / 2.0, nu))}
+
+
+def check_counts(st):
+    assert st["max_z"] <= st["z_bound"], st
+    assert st["chi2_lo"] <= st["chi2"] <= st["chi2_hi"], st
+
+
+def check_batches(st):
+    assert st["max_t"] <= st["t_bound"], st
+    assert st["mean_t2_lo"] <= st["mean_t2"] <= st["mean_t2_hi"], st
+    assert st["score"] <= st["score_bound"], st
+    assert abs(st["t_sum"]) <= st["t_sum_bound"], st
+
+
+# ----------------------------------------------------------------- what a test asserts ----
+def evaluate_ab(which, jm, ab, ctr, n_batch, ref):
+    """Scenes A and B: a run in batches (run_batches) against ref = (T, p). ALPHA is shared by three
+    groups: the absorb counts (count_stats), the absorbed and escaped counters (one binomial: they
+    sum to N) and the tracks (batch_stats). A voxel's track has at least N T_v / DIAG contributing
+    photons, none of which leaves more than the voxel's diagonal: that is its event count."""
+    t, p = ref
+    n = n_batch * len(jm)
+    a = ALPHA / 3.0
+    return {"which": which, "n": n,
+            "counts": count_stats(ab.sum(axis=0), p, n, a),
+            "z_absorbed": binomial_z(ctr["absorbed"], p.sum(), n),
+            "z_escaped": binomial_z(ctr["escaped"], 1.0 - p.sum(), n), "z_bound": binomial_bound(a),
+            "tracks": batch_stats(jm, n_batch * t, n * t / DIAG, a, slop=n_batch * B_TRACK_SLOP if which == "b" else 0.0),
+            "absorb_off_support": float(ab.sum(axis=0)[p == 0.0].sum()),
+            "jmean_off_support": float(jm.sum(axis=0)[t == 0.0].sum()),
+            "faults": ctr.get("faults", 0), "lost": n - ctr["absorbed"] - ctr["escaped"]}
+
+
+def check_ab(st):
+    """The assertions of scenes A and B on evaluate_ab's statistics."""
+    assert st["faults"] == 0 and st["lost"] == 0, st
+    assert st["absorb_off_support"] == 0.0 and st["jmean_off_support"] == 0.0, st
+    for group in ("counts", "tracks"):  # the pooling rule's conditions, on absorptions and on tracks
+        if st["which"] == "a":
+            assert st[group]["n_pooled"] == 0 and st[group]["bins"] == N_VOXELS, st[group]
+        else:
+            assert st[group]["pooled_share"] < B_POOL_CAP, st[group]
+    check_counts(st["counts"])
+    assert abs(st["z_absorbed"]) <= st["z_bound"] and abs(st["z_escaped"]) <= st["z_bound"], st
+    check_batches(st["tracks"])
+
+
+def evaluate_c(jm, ab, ctr, mua=None):
+    """Scene C: d = mua(v) jmean[v] - absorb[v] per batch has expectation zero in every voxel (the
+    track-length and the collision estimator of absorption). Voxels in which both estimators saw
+    fewer than MIN_EVENTS events over all batches (absorptions; tracks, at least jmean / DIAG of
+    them) are pooled."""
+    mua = mua_c() if mua is None else mua
+    d = mua[None] * jm - ab
+    events = np.maximum(ab.sum(axis=0), jm.sum(axis=0) / DIAG)
+    st = batch_stats(d, np.zeros_like(mua), events, ALPHA)
+    st["faults"] = ctr.get("faults", 0)
+    st["absorb_sum"], st["track_sum"] = float(ab.sum()), float((mua[None] * jm).sum())
+    return st
+
+
+def check_c(st):
+    assert st["faults"] == 0, st
+    assert st["n_pooled"] <= C_POOL_CAP * N_VOXELS, st
+    check_batches(st)
