@@ -587,13 +587,16 @@ __global__ __launch_bounds__(1024) void bk_scan(const uint32_t* __restrict__ til
   }
 }
 
-// ---- bk_place: bucket ids in tile order ------------------------------------------------------
+// ---- bk_place: bucket ids and fills in tile order --------------------------------------------
 // Block b takes a contiguous range of ids in passes of BIN_THREADS * 8: LDS ranks per tile,
-// one global reservation per (pass, tile), then the ids are written to order[].
+// one global reservation per (pass, tile), then {id, fill} is written to order[]. The fills are
+// final here (the transport kernel that wrote them has ended), so bk_reduce gets a bucket's id
+// and fill from one coalesced load and never reads bucket_fill[id] behind the id.
 __global__ __launch_bounds__(BIN_THREADS) void bk_place(const uint32_t* __restrict__ bucket_tile,
+                                                        const uint32_t* __restrict__ bucket_fill,
                                                         const uint32_t* __restrict__ dep_ctl, uint32_t n_buckets,
                                                         uint32_t n_tiles, uint32_t* __restrict__ cursor,
-                                                        uint32_t* __restrict__ order) {
+                                                        uint2* __restrict__ order) {
   __shared__ uint32_t cnt[MAX_DIRECT_TILES];
   __shared__ uint32_t base[MAX_DIRECT_TILES];
   const uint32_t used = dep_ctl[0] < n_buckets ? dep_ctl[0] : n_buckets;
@@ -604,11 +607,12 @@ __global__ __launch_bounds__(BIN_THREADS) void bk_place(const uint32_t* __restri
   for (uint32_t t = threadIdx.x; t < n_tiles; t += blockDim.x) cnt[t] = 0;
   __syncthreads();
   for (uint32_t p = b0; p < b1; p += BIN_THREADS * PER_THREAD) {
-    uint32_t tile[PER_THREAD], rank[PER_THREAD];
+    uint32_t tile[PER_THREAD], fill[PER_THREAD], rank[PER_THREAD];
 #pragma unroll
     for (int k = 0; k < PER_THREAD; ++k) {
       const uint32_t i = p + threadIdx.x + k * BIN_THREADS;
       tile[k] = i < b1 ? bucket_tile[i] : TILE_INVALID;
+      fill[k] = i < b1 ? bucket_fill[i] : 0u;
       rank[k] = tile[k] < n_tiles ? atomicAdd(&cnt[tile[k]], 1u) : 0u;
     }
     __syncthreads();
@@ -621,7 +625,7 @@ __global__ __launch_bounds__(BIN_THREADS) void bk_place(const uint32_t* __restri
 #pragma unroll
     for (int k = 0; k < PER_THREAD; ++k) {
       const uint32_t i = p + threadIdx.x + k * BIN_THREADS;
-      if (tile[k] < n_tiles) order[base[tile[k]] + rank[k]] = i;
+      if (tile[k] < n_tiles) order[base[tile[k]] + rank[k]] = make_uint2(i, fill[k]);
     }
     __syncthreads();
   }
@@ -630,71 +634,140 @@ __global__ __launch_bounds__(BIN_THREADS) void bk_place(const uint32_t* __restri
 // ---- bk_reduce: one piece (buckets of one tile) per block, fp64 LDS sums into jmean --------
 // (blockDim.x must be 1024)
 constexpr uint32_t RED_THREADS = 1024;  // bk_reduce's block size
-// One wave per bucket (round 4): wave w of the block takes buckets w, w + 16, w + 32, ... of the
-// piece, RED_GROUP at a time; a bucket's id and fill are scalar loads and its 256 records four
-// coalesced 512-B loads per wave. The next group's records are loaded before this group's LDS
-// adds are issued (software pipeline), so each wave keeps 2 * RED_GROUP * 4 records per lane
-// in flight and its memory latency overlaps its own LDS atomics; no ids/fills staging in LDS
-// and no block barrier inside a piece. Sums are the same fp64 LDS adds in a different order.
+// One wave per bucket (round 4). Wave w of the block takes a contiguous run of the piece's
+// buckets. Lane l loads the {id, fill} entry of the run's bucket 64 * k + l (one coalesced load
+// per batch of 64 buckets, issued a whole batch before its first use), and a bucket's id and fill
+// are v_readlane of those registers: no load stands between a bucket and its records. The records
+// are loaded RED_GROUP buckets at a time, four per lane (a 16-B load of values and an 8-B load of
+// voxels per bucket), unconditionally, so a group's loads are one basic block; the fill is the
+// predicate of the LDS add. Two groups alternate: one is loaded while the other is added, and the
+// only waits inside the loops are counted (vmcnt >= 2 * RED_GROUP: the newer group stays in
+// flight). No ids/fills staging in LDS and no block barrier inside a piece. Sums are the same fp64
+// LDS adds in a different order.
+// Until round 9 the id was a vector load and the fill a scalar load behind it, each followed by a
+// full wait, and the record loads sat in `slot < fill` branches, so a wave made two dependent
+// round trips per bucket and issued no LDS add while a load was in flight: 1.39 records per
+// CU-cycle on 32 CUs, where this loop reaches the 2.36-2.40 of the fp64 LDS adds themselves
+// (tools/microbench/fold_bench.hip, lds_atomic_bench.hip; profiles/r09_fold/). RED_GROUP 2, 4 and
+// 8 measure the same there.
 // (Measured and removed in round 5: a block-wide staged variant with 16 loads in flight per
 // thread, 5 % slower; non-temporal record loads, no change, profiles/r03_s3/nt_ab.txt.)
-constexpr int RED_GROUP = 4;
+#ifndef SMCRT_RED_GROUP
+#define SMCRT_RED_GROUP 4
+#endif
+constexpr int RED_GROUP = SMCRT_RED_GROUP;  // buckets a wave loads ahead of its LDS adds
+// (a group lies within one batch of 64 ids, and a full batch is an even number of groups: its
+// last trip takes the odd group from the batch itself)
+static_assert(RED_GROUP >= 1 && 32 % RED_GROUP == 0, "RED_GROUP must divide 32");
+
+// Records 4 * lane .. 4 * lane + 3 of one bucket: two loads per lane (16 B of values and 8 B of
+// voxels; 8-byte records: two 16-B loads).
+struct RedQuad {
+#if SMCRT_REC6
+  uint4 v;  // f32 values
+  uint2 i;  // u16 voxels within the tile
+#else
+  ulonglong2 a, b;
+#endif
+};
+// Every slot of a bucket of the pool is in bounds, so the loads need no condition; red_add leaves
+// out the slots at and past the bucket's fill.
+__device__ __forceinline__ RedQuad red_load(const unsigned long long* __restrict__ pool, uint32_t id, uint32_t lane) {
+  const unsigned long long* __restrict__ base = pool + ((uint64_t)id << BUCKET_SHIFT);
+  RedQuad q;
+#if SMCRT_REC6
+  q.v = ((const uint4*)base)[lane];
+  q.i = ((const uint2*)((const uint32_t*)base + BUCKET_RECORDS))[lane];
+#else
+  q.a = ((const ulonglong2*)base)[2 * lane];
+  q.b = ((const ulonglong2*)base)[2 * lane + 1];
+#endif
+  return q;
+}
+__device__ __forceinline__ void red_add(double* acc, const RedQuad& q, uint32_t lane, uint32_t fill) {
+#if SMCRT_REC6
+  const uint32_t val[4] = {q.v.x, q.v.y, q.v.z, q.v.w};
+  const uint32_t vox[4] = {q.i.x & 0xFFFFu, q.i.x >> 16, q.i.y & 0xFFFFu, q.i.y >> 16};
+#else
+  const uint32_t val[4] = {(uint32_t)q.a.x, (uint32_t)q.a.y, (uint32_t)q.b.x, (uint32_t)q.b.y};
+  const uint32_t vox[4] = {(uint32_t)(q.a.x >> 32), (uint32_t)(q.a.y >> 32), (uint32_t)(q.b.x >> 32),
+                           (uint32_t)(q.b.y >> 32)};
+#endif
+#pragma unroll
+  for (uint32_t r = 0; r < 4; ++r)
+    if (4 * lane + r < fill) atomicAdd(&acc[vox[r] & (TILE_VOXELS - 1)], (double)__uint_as_float(val[r]));
+}
+
 __global__ __launch_bounds__(RED_THREADS) void bk_reduce(const unsigned long long* __restrict__ pool,
-                                                  const uint32_t* __restrict__ order,
-                                                  const uint32_t* __restrict__ bucket_fill,
+                                                  const uint2* __restrict__ order,
                                                   const Piece* __restrict__ pieces,
                                                   const uint32_t* __restrict__ dep_ctl, uint64_t n_voxels,
                                                   double* __restrict__ jmean, unsigned long long* __restrict__ busy) {
   const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
   __shared__ double acc[TILE_VOXELS];
   const uint32_t n_pieces = dep_ctl[2];
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint32_t lane = threadIdx.x & 63, w = uniform(threadIdx.x >> 6);
   constexpr uint32_t NW = RED_THREADS / 64;  // waves per block
-  constexpr int NR = RED_GROUP * 4;        // records per lane per group
+  constexpr uint32_t G = RED_GROUP;
   for (uint32_t pi = blockIdx.x; pi < n_pieces; pi += gridDim.x) {
     const Piece p = pieces[pi];
     for (uint32_t i = threadIdx.x; i < TILE_VOXELS; i += blockDim.x) acc[i] = 0.0;
     __syncthreads();
-    // group g of this wave: buckets w + NW * (RED_GROUP * g + u), u < RED_GROUP
-    auto fetch = [&](uint32_t g, unsigned long long* x) {
+    // this wave's run of the piece: buckets b0 .. b0 + n - 1
+    const uint32_t per = (p.count + NW - 1) / NW;
+    const uint32_t b0 = w * per < p.count ? w * per : p.count;
+    const uint32_t n = p.count - b0 < per ? p.count - b0 : per;
+    if (n) {
+      const uint2* __restrict__ ord = order + p.start + b0;
+      // batch k: lane l loads {id, fill} of the run's bucket 64 * k + l; past the run's end, of
+      // the run's last bucket (which exists, and is in the cache), whose fill open() makes 0
+      auto batch = [&](uint32_t k) {
+        const uint32_t i = 64u * k + lane;
+        return ord[i < n ? i : n - 1];
+      };
+      auto open = [&](uint32_t k, const uint2& raw) {
+        return make_uint2(raw.x, 64u * k + lane < n ? raw.y : 0u);
+      };
+      // group j of the batch held in e: its buckets G * j + u, u < G. Buckets past the run's end
+      // are "last bucket, fill 0": loaded from the cache, never added.
+      auto fetch = [&](const uint2& e, uint32_t j, RedQuad* x, uint32_t* f) {
 #pragma unroll
-      for (int u = 0; u < RED_GROUP; ++u) {
-        const uint32_t b = w + NW * (RED_GROUP * g + (uint32_t)u);
-        uint32_t f = 0, id = 0;
-        if (b < p.count) {
-          id = uniform(order[p.start + b]);
-          f = uniform(bucket_fill[id]);
+        for (uint32_t u = 0; u < G; ++u) {
+          const uint32_t k = (G * j + u) & 63u;
+          const uint32_t id = __builtin_amdgcn_readlane(e.x, k);
+          f[u] = __builtin_amdgcn_readlane(e.y, k);
+          x[u] = red_load(pool, id, lane);
         }
-        const unsigned long long* __restrict__ base = pool + ((uint64_t)id << BUCKET_SHIFT);
-#if SMCRT_REC6
-        const uint32_t* __restrict__ bv = (const uint32_t*)base;
-        const uint16_t* __restrict__ bi = (const uint16_t*)(bv + BUCKET_RECORDS);
+      };
+      auto add = [&](const RedQuad* x, const uint32_t* f) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const uint32_t slot = lane + 64u * (uint32_t)r;
-          x[4 * u + r] = slot < f ? ((unsigned long long)bi[slot] << 32) | bv[slot] : ~0ull;
+        for (uint32_t u = 0; u < G; ++u) red_add(acc, x[u], lane, f[u]);
+      };
+      // Two groups per trip, each loaded while the other is added; no register is copied, so the
+      // only waits in the loops are counted ones that leave the newer group's loads in flight.
+      // The next batch's entries are loaded when a batch begins and opened in its last trip,
+      // which fetches that batch's first group.
+      const uint32_t nb = (n + 63u) / 64u;
+      uint2 e = open(0, batch(0));
+      RedQuad xa[G], xb[G];
+      uint32_t fa[G], fb[G];
+      fetch(e, 0, xa, fa);
+      for (uint32_t kb = 0; kb < nb; ++kb) {
+        const uint2 en = batch(kb + 1u);
+        const uint32_t m = n - 64u * kb < 64u ? n - 64u * kb : 64u;
+        const uint32_t gb = (m + G - 1) / G;  // groups of this batch; group 0 is in xa
+        uint32_t j = 0;
+        for (; j + 2 < gb; j += 2) {
+          fetch(e, j + 1, xb, fb);
+          add(xa, fa);
+          fetch(e, j + 2, xa, fa);
+          add(xb, fb);
         }
-#else
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const uint32_t slot = lane + 64u * (uint32_t)r;
-          x[4 * u + r] = slot < f ? base[slot] : ~0ull;
-        }
-#endif
-      }
-    };
-    const uint32_t ng = (p.count + NW * RED_GROUP - 1) / (NW * RED_GROUP);  // groups of the piece (wave 0's count)
-    unsigned long long cur[NR];
-    fetch(0, cur);
-    for (uint32_t g = 0; g < ng; ++g) {
-      unsigned long long nxt[NR];
-      if (g + 1 < ng) fetch(g + 1, nxt);
-#pragma unroll
-      for (int k = 0; k < NR; ++k)
-        if (cur[k] != ~0ull) atomicAdd(&acc[(uint32_t)(cur[k] >> 32) & (TILE_VOXELS - 1)], (double)__uint_as_float((uint32_t)cur[k]));
-      if (g + 1 < ng) {
-#pragma unroll
-        for (int k = 0; k < NR; ++k) cur[k] = nxt[k];
+        fetch(e, j + 1, xb, fb);  // (gb odd: a group past the run's end, which is in this batch)
+        add(xa, fa);
+        e = open(kb + 1u, en);
+        fetch(e, 0, xa, fa);
+        add(xb, fb);
       }
     }
     __syncthreads();

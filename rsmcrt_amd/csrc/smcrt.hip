@@ -147,7 +147,7 @@ struct smcrt_scene : ScenePlan {
   // bucketed path: per slot the tile of each bucket id (bucket fills use d_chunk_fill, the
   // per-tile bucket counts d_bin_counts); shared by the serial folds: ids in tile order
   DevBuf<uint32_t> d_bucket_tile[MAX_SLOTS];
-  DevBuf<uint32_t> d_order;
+  DevBuf<uint2> d_order;  // {id, fill} per bucket in tile order (bk_place)
   DevBuf<uint32_t> d_chunk_fill[MAX_SLOTS];
   DevBuf<uint32_t> d_dep_ctl[MAX_SLOTS];  // [0] chunks taken [1] overflow [2] pieces [3] records
   DevBuf<uint32_t> d_tile_count;  // n_tiles
@@ -656,7 +656,7 @@ static bool ensure_pool(smcrt_scene* s, uint64_t records) {
     else if (ok)  // chunk fills, per slot
       ok = s->d_chunk_fill[i].alloc(chunks) == hipSuccess;
   }
-  if (ok && s->bucketed)  // the tile-ordered bucket id list (folds are serial)
+  if (ok && s->bucketed)  // the tile-ordered list of bucket ids and fills (folds are serial)
     ok = s->d_order.alloc(buckets) == hipSuccess;
   else if (ok)  // the tile-sorted copy of the records
     ok = s->d_sorted.alloc(cap) == hipSuccess;
@@ -771,11 +771,11 @@ static int enqueue_fold(smcrt_scene* s, const KParams& K, double* jmean, hipStre
   if (K.bucket_tiles) {  // bucketed: list each tile's buckets, then sum them
     hipLaunchKernelGGL(bk_scan, dim3(1), dim3(1024), 0, fs, s->d_bin_counts[sl], s->n_tiles, s->d_tile_start,
                        s->d_tile_count, s->d_pieces, s->d_dep_ctl[sl]);
-    hipLaunchKernelGGL(bk_place, dim3(BIN_BLOCKS), dim3(BIN_THREADS), 0, fs, s->d_bucket_tile[sl], s->d_dep_ctl[sl],
-                       K.n_buckets, s->n_tiles, s->d_tile_count, s->d_order);
+    hipLaunchKernelGGL(bk_place, dim3(BIN_BLOCKS), dim3(BIN_THREADS), 0, fs, s->d_bucket_tile[sl], s->d_chunk_fill[sl],
+                       s->d_dep_ctl[sl], K.n_buckets, s->n_tiles, s->d_tile_count, s->d_order);
 #ifndef SMCRT_ABL_NO_FOLD  // timing ablation only: records are never summed (not exact)
-    hipLaunchKernelGGL(bk_reduce, dim3(1024), dim3(RED_THREADS), 0, fs, s->d_pool[sl], s->d_order, s->d_chunk_fill[sl],
-                       s->d_pieces, s->d_dep_ctl[sl], nv, jmean, s->d_queue + Q_FOLD_TICKS);
+    hipLaunchKernelGGL(bk_reduce, dim3(1024), dim3(RED_THREADS), 0, fs, s->d_pool[sl], s->d_order, s->d_pieces,
+                       s->d_dep_ctl[sl], nv, jmean, s->d_queue + Q_FOLD_TICKS);
 #endif
   } else {
     if (!K.hist_tiles)  // else the transport kernel built the counts
