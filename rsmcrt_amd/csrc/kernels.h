@@ -10,21 +10,12 @@
 #include "scene_internal.h"
 #include "transport.h"
 #include "deposit.h"
+#include "lanekit.h"
 #include "paths.h"
 #include "phasor.h"
 
 using namespace smcrt;
 // ------------------------------------------------------------------ kernel ---------
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 #ifdef SMCRT_DIAG
 // (one copy per kinst.hip object; kinst_diag_* gathers them)
@@ -108,7 +99,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
   const double* yf = K.yface;
   const double* zf = K.zface;
   int hist_off = 0;  // doubles of sh_dyn before the wave histograms
-  if constexpr (LDS_FACES) {
+  if constexpr (LDS_FACES) {  // (lanekit.h's stage_media_faces, kept as text here)
     // per-lane (divergent) lookups go to LDS, never to vector memory: a vector load would
     // make the wave wait for all of its outstanding deposit atomics
     const int np = 4 * K.n_top;
@@ -134,7 +125,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
   }
   if (K.n_dets) hist_off += 3 * 256;
   // deposit state: the sorted path's per-wave tile histogram (hist_tiles words) or the
-  // bucketed path's per-block word per tile (cur | next | fill: 2 * bucket_tiles words)
+  // bucketed path's per-block word per tile (cur | next | fill: 2 * bucket_tiles words).
+  // (Kept as locals, not lanekit.h's DepositState: as members of a struct they are promoted to
+  // registers in another order, and this kernel's register allocation follows that order.)
   const uint32_t wave_words = K.bucket_tiles ? 0u : K.hist_tiles;
   const uint32_t dep_words = K.bucket_tiles ? 2 * K.bucket_tiles : 4 * K.hist_tiles;  // the block's
   uint32_t* const whist = (uint32_t*)(sh_dyn + hist_off) + (threadIdx.x >> 6) * wave_words;
@@ -150,20 +143,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
     if (K.ctab)
       for (int i = threadIdx.x; i < CTAB_DOUBLES; i += blockDim.x) ctab[i] = K.ctab[i];
   }
-#pragma unroll
-  for (int c = 0; c < LC_N; ++c) sh->ctr[c][threadIdx.x] = 0;
-#pragma unroll
-  for (int c = 0; c < LU_N; ++c) sh->u[c][threadIdx.x] = 0;
+  zero_counters(sh);
   __syncthreads();
 
   Lane L;
-  L.st = ST_FETCH; L.pend = false; L.seg = false; L.fault = false; L.tflag = false;
-  L.pos = L.dir = L.ssp = L.old = v3(0.0, 0.0, 0.0);
-  L.weight = 1.0; L.tau = L.taurun = L.d = L.minabs = 0.0;
-  L.xcell = L.ycell = L.zcell = L.layer = L.old_layer = L.new_layer = L.Ls = 0;
-  L.hop = L.loopc = L.dda_it = 0;
-  L.sd = L.slen = 0.0;
-  L.rng.init(0);
+  lane_reset(L, ST_FETCH);
   const bool binned = K.rec_pool != nullptr;  // (set only when jmean is tallied)
   RecLog W;
   W.chunk = LOG_NONE; W.fill = 0;
@@ -196,6 +180,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
   for (;; ++w_iters) {
     DIAG_T(8);
     // ---- photon fetch (wave-aggregated work queue) ------------------------------------
+    // (lanekit.h's fetch_photons with the XSRC origin split, kept as text here: see that header)
     // A wave takes FETCH_CHUNK photon indices per (returning) queue atomic and hands them
     // to its lanes as they free up: a returning atomic waits for all of the wave's
     // outstanding deposits, so it must be rare.
@@ -578,8 +563,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
           LCTR(LC_FRES)++;
           const double Rf = fresnel(L.dir, N, n1, n2);
           if (L.rng.next(K.key0, K.key1) <= Rf) {  // reflect :42-55, :304-316
-            const double s2 = 2.0 * dot(N, L.dir);
-            L.dir = L.dir - smul(s2, N);
+            L.dir = reflect_dir(L.dir, N);
             LCTR(LC_REFL)++;
             if (K.n_dets) { startp[0] = L.pos.x; startp[256] = L.pos.y; startp[512] = L.pos.z; }
             if constexpr (PHAS) {
@@ -594,13 +578,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
               L.st = ST_H0;  // arrives in P8
             }
           } else {  // refract :57-84, transmit :284-303
-            const double eta = n1 / n2;
-            V3 Nt = N;
-            double c1 = dot(Nt, L.dir);
-            if (c1 < 0.0) c1 = -c1;
-            else Nt = smul(-1.0, N);
-            const double c2 = sqrt(1.0 - (eta * eta) * (1.0 - c1 * c1));
-            L.dir = smul(eta, L.dir) + smul(eta * c1 - c2, Nt);
+            L.dir = refract_dir(L.dir, N, n1, n2);
             L.layer = L.new_layer;
             L.st = ST_X1;
             start_segment<GM>(K, L, sh, L.pos, L.d);
@@ -659,8 +637,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
         if (binned) {
           if (K.bucket_tiles) emit_bucketed(K, C, WB, dep, vox, val, overflow, bstate);
           else emit_deposits(K, C, W, dep, vox, val, overflow, whist);
-        }
-        else if (dep) {
+        } else if (dep) {
           double* const jm = C->jmean;
           if (jm) atomic_add_nr(jm + vox, val);
         }
@@ -744,6 +721,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
     // ---- P7: photon events (interaction, tauint2 entry, emission, completion) ----------
     // These are the expensive, rare program points; a wave runs them together once enough
     // lanes wait for one (or nothing else is left), instead of paying for them every trip.
+    // (lanekit.h's events_due, kept as text here)
     {
       const bool ev = (L.st == ST_INTERACT || L.st == ST_T2 || L.st == ST_EMIT || L.st == ST_DONE);
       const uint64_t evm = __ballot(ev);
@@ -843,28 +821,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
           else { L.st = ST_LAYER; L.pend = true; }
         }
         if (L.st == ST_DONE) {  // photon finished
-          if (L.fault) { LU(LU_STATUS) = 3; LCTR(LC_FAULTS)++; }
-          else if (LU(LU_STATUS) == 0) { LU(LU_STATUS) = 2; LCTR(LC_ESCAPED)++; }
-          LCTR(LC_PHOTONS)++;
-          LCTR(LC_DRAWS) += L.rng.draws;
+          close_photon(L, sh);
 #ifdef SMCRT_DIAG
           if (C->done_time)
             C->done_time[(((uint64_t)L.rng.pid_hi << 32) | L.rng.pid_lo) - C->done_base] = __builtin_amdgcn_s_memrealtime();
 #endif
-          smcrt_photon_record* const records = C->records;
-          if ((K.flags & SMCRT_FLAG_RECORD_PHOTONS) && records) {
-            const uint64_t pid = ((uint64_t)L.rng.pid_hi << 32) | L.rng.pid_lo;
-            smcrt_photon_record* r = records + (pid - C->first_photon);
-            r->pos[0] = L.pos.x; r->pos[1] = L.pos.y; r->pos[2] = L.pos.z;
-            r->dir[0] = L.dir.x; r->dir[1] = L.dir.y; r->dir[2] = L.dir.z;
-            r->weight = L.weight;
-            r->cell[0] = L.xcell; r->cell[1] = L.ycell; r->cell[2] = L.zcell;
-            r->layer = L.layer;
-            r->nscatt = LU(LU_NSCATT);
-            r->bounces = LU(LU_BOUNCES);
-            r->draws = L.rng.draws;
-            r->status = LU(LU_STATUS);
-          }
+          write_record(K, C, L, sh, L.pos);
           if constexpr (HIST) {  // the range trigger: the whole path of a photon of the tracked range
             const uint64_t pid = ((uint64_t)L.rng.pid_hi << 32) | L.rng.pid_lo;
             if (pid - C->range_first < C->range_count)
@@ -905,7 +867,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COOP ? SMCR
     atomicAdd(&g_diag[70], 1ull);  // waves
   }
 #endif
-  // ---- per-wave counter reduction ------------------------------------------------------
+  // ---- per-wave counter reduction (lanekit.h's flush_counters with w_sdf, kept as text) ----
   if (binned && K.bucket_tiles) {  // segments of this launch (the host's lean-kernel choice)
     const uint32_t u = wave_sum_u32(LCTR(LC_UPD));
     if (lane_id == 0 && u) atomicAdd(C->dep_ctl + 6, u);

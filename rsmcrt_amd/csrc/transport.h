@@ -408,6 +408,23 @@ __device__ __forceinline__ double fresnel(V3 I, V3 N, double n1, double n2) {
   return 0.5 * (f1 + f2);
 }
 
+// reflect, surfaces.f90:42-55
+__device__ __forceinline__ V3 reflect_dir(V3 dir, V3 N) {
+  const double s2 = 2.0 * dot(N, dir);
+  return dir - smul(s2, N);
+}
+
+// refract, surfaces.f90:57-84 (the caller has ruled out total internal reflection: fresnel() < 1)
+__device__ __forceinline__ V3 refract_dir(V3 dir, V3 N, double n1, double n2) {
+  const double eta = n1 / n2;
+  V3 Nt = N;
+  double c1 = dot(Nt, dir);
+  if (c1 < 0.0) c1 = -c1;
+  else Nt = smul(-1.0, N);
+  const double c2 = sqrt(1.0 - (eta * eta) * (1.0 - c1 * c1));
+  return smul(eta, dir) + smul(eta * c1 - c2, Nt);
+}
+
 __device__ __forceinline__ double pointsep(V3 a, V3 b) {
   const double dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
   return sqrt(dx * dx + dy * dy + dz * dz);
@@ -472,9 +489,11 @@ struct Lane {
 enum : int { LC_PHOTONS = 0, LC_RETRIES, LC_SCATTERS, LC_ABSORBED, LC_TAU, LC_FRES, LC_REFL, LC_BABORT,
              LC_FAULTS, LC_DRAWS, LC_HITS, LC_ESCAPED, LC_UPD, LC_N };
 enum : int { LU_INTER = 0, LU_BOUNCES, LU_NSCATT, LU_STATUS, LU_ORIGIN, LU_N };  // per-photon fields
-struct LaneShared {
+struct LaneCounters {  // all a kernel without tauint2's bounce abort needs (voxel.h, mesh.h)
   uint32_t ctr[LC_N][256];
   uint32_t u[LU_N][256];
+};
+struct LaneShared : LaneCounters {
   double entry[6][256];  // tauint2 entry pos/dir, restored on a bounce abort (inttau2.f90:313-315)
   // (startPos of the detector segments, inttau2.f90:59,125-131, is in dynamic LDS and only
   // allocated when the scene has detectors)
@@ -880,7 +899,7 @@ __device__ __forceinline__ void scatter(const KParams& K, Lane& L, double hgg) {
 // length `dlen` along L.dir; the segment itself runs in the DDA phase. Returns true if the
 // lane must wait for the DDA.
 template <int GM>
-__device__ __forceinline__ bool start_segment(const KParams& K, Lane& L, LaneShared* sh, V3 p, double dlen) {
+__device__ __forceinline__ bool start_segment(const KParams& K, Lane& L, LaneCounters* sh, V3 p, double dlen) {
   LCTR(LC_UPD)++;
   V3 old = v3(p.x + K.xmax, p.y + K.ymax, p.z + K.zmax);
   int32_t ci = cell_of<GM>(old.x, K.nx, K.xmax, K.inv2x, K.fex), cj = cell_of<GM>(old.y, K.ny, K.ymax, K.inv2y, K.fey),

@@ -6,11 +6,12 @@
 // sd = 0 and slen = tau_left / kappa), looks up the label of each voxel it enters and meets an
 // interface wherever the refractive index changes, with the normal of the crossed voxel wall.
 //
-// Scheduling is transport_kernel's: a persistent grid, wave-aggregated fetch from C->queue, one
-// lane per photon refilled as photons end, per-block counters flushed at the end, deposits
-// through the plan's regime (buckets, sorted records or fp64 atomics). A lane does one piece or
-// one event per trip; the rare events (emission, flight start, Fresnel decision, interaction,
-// completion) run together once enough lanes wait for one.
+// Scheduling is the photon-lane scaffold of lanekit.h, which transport_kernel uses too: a persistent
+// grid, wave-aggregated fetch from C->queue, one lane per photon refilled as photons end, per-block
+// counters flushed at the end, deposits through the plan's regime (buckets, sorted records or fp64
+// atomics). A lane does one piece or one event per trip; the rare events (emission, flight start,
+// Fresnel decision, interaction, completion) run together once enough lanes wait for one. What is
+// here is the kernel's own: the walk stage, the Fresnel wall and the flight start.
 //
 // Included by kinst.hip's part 4 only (after kernels.h), so no other kernel sees this file.
 #pragma once
@@ -33,19 +34,13 @@ enum : uint32_t {
   VS_DONE,      // photon finished: tallies, record, next photon
 };
 
-// LDS-resident per-lane counters and per-photon fields (transport.h LCTR / LU index them)
-struct VoxShared {
-  uint32_t ctr[LC_N][256];
-  uint32_t u[LU_N][256];
-};
-
 template <int GM, bool XSRC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES_PER_EU_VOXEL))) void voxel_kernel(
     KParams K, const smcrt_sdf_node* __restrict__ nodes, const ProgOp* __restrict__ prog,
     const smcrt_detector* __restrict__ dets, const int64_t* __restrict__ det_off, const KCold* __restrict__ C) {
   (void)nodes; (void)prog;  // (transport_kernel's argument list; a voxel scene has no SDF)
-  __shared__ VoxShared shm;
-  VoxShared* sh = &shm;
+  __shared__ LaneCounters shm;
+  LaneCounters* sh = &shm;
   const bool survival = (K.flags & SMCRT_FLAG_SURVIVAL_BIAS) != 0;
   const bool pathlen = (K.flags & SMCRT_FLAG_PATHLENGTH) != 0;
   const int lane_id = threadIdx.x & 63;
@@ -53,81 +48,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
   // [media | faces] | deposit words. Everything a lane looks up per crossing but the label is in
   // LDS: a vector load would wait for the wave's outstanding record stores and atomics.
   extern __shared__ double sh_dyn[];
-  const int np = 4 * K.n_top;
-  const int nf = (K.nx + 1) + (K.ny + 1) + (K.nz + 2);
-  {
-    const double* gp = (const double*)K.props;
-    for (int i = threadIdx.x; i < np; i += blockDim.x) sh_dyn[i] = gp[i];
-    for (int i = threadIdx.x; i < nf; i += blockDim.x) sh_dyn[np + i] = K.xface[i];  // faces are contiguous
-  }
-  const TopProps* const props = (const TopProps*)sh_dyn;
-  const double* const xf = sh_dyn + np;
-  const double* const yf = xf + (K.nx + 1);
-  const double* const zf = yf + (K.ny + 1);
-  const int hist_off = np + nf;
-  const uint32_t wave_words = K.bucket_tiles ? 0u : K.hist_tiles;
-  uint32_t* const whist = (uint32_t*)(sh_dyn + hist_off) + (threadIdx.x >> 6) * wave_words;
-  unsigned long long* const bstate = (unsigned long long*)(sh_dyn + hist_off);
-  if (K.bucket_tiles) init_buckets(K, C, bstate);
-  else
-    for (uint32_t i = threadIdx.x; i < 4 * K.hist_tiles; i += blockDim.x) ((uint32_t*)(sh_dyn + hist_off))[i] = 0;
-#pragma unroll
-  for (int c = 0; c < LC_N; ++c) sh->ctr[c][threadIdx.x] = 0;
-#pragma unroll
-  for (int c = 0; c < LU_N; ++c) sh->u[c][threadIdx.x] = 0;
+  const StagedMedia M = stage_media_faces(K, sh_dyn);
+  const TopProps* const props = M.props;
+  const double *const xf = M.xf, *const yf = M.yf, *const zf = M.zf;
+  DepositState D;
+  D.init(K, C, sh_dyn + M.doubles);
+  zero_counters(sh);
   __syncthreads();
 
   const uint8_t* __restrict__ const labels = C->vox_labels;
   Lane L;
-  L.st = VS_FETCH; L.pend = false; L.seg = false; L.fault = false; L.tflag = false;
-  L.pos = L.dir = L.ssp = L.old = v3(0.0, 0.0, 0.0);
-  L.weight = 1.0; L.tau = L.taurun = L.d = L.minabs = 0.0;
-  L.xcell = L.ycell = L.zcell = L.layer = L.old_layer = L.new_layer = L.Ls = 0;
-  L.hop = L.loopc = L.dda_it = 0;
-  L.sd = L.slen = 0.0;
-  L.rng.init(0);
-  const bool binned = K.rec_pool != nullptr;  // (set only when jmean is tallied)
-  RecLog W;
-  W.chunk = LOG_NONE; W.fill = 0;
-  BucketLog WB;
-  WB.next = WB.end = 0;
-  uint32_t overflow = 0;
-  uint32_t w_dep = 0, w_iters = 0;  // wave totals (scalar registers)
-  uint64_t chunk_base = 0;          // wave-uniform photon chunk
+  lane_reset(L, VS_FETCH);
+  uint32_t w_iters = 0;     // wave total (a scalar register)
+  uint64_t chunk_base = 0;  // wave-uniform photon chunk
   uint32_t chunk_left = 0;
 
   for (;; ++w_iters) {
-    // ---- photon fetch (wave-aggregated work queue; transport_kernel's) --------------------
-    {
-      uint64_t need = __ballot(L.st == VS_FETCH);
-      while (need) {
-        if (chunk_left == 0) {
-          unsigned long long base = 0;
-          if (lane_id == 0) base = atomicAdd(C->queue, (unsigned long long)SMCRT_FETCH_CHUNK);
-          chunk_base = __shfl(base, 0, 64);
-          const uint64_t n_photons = C->n_photons;
-          chunk_left = (chunk_base < n_photons)
-                           ? (uint32_t)((n_photons - chunk_base) < SMCRT_FETCH_CHUNK ? (n_photons - chunk_base)
-                                                                                       : SMCRT_FETCH_CHUNK)
-                           : 0u;
-          if (chunk_left == 0) {  // queue exhausted
-            if (L.st == VS_FETCH) L.st = VS_IDLE;
-            break;
-          }
-        }
-        const uint32_t n = __popcll(need);
-        const uint32_t take = n < chunk_left ? n : chunk_left;
-        const uint64_t rank = __popcll(need & ((1ull << lane_id) - 1ull));
-        if (L.st == VS_FETCH && rank < take) {
-          L.rng.init(C->first_photon + chunk_base + rank);
+    if (!fetch_photons<VS_FETCH, VS_IDLE>(C, lane_id, L, chunk_base, chunk_left, [&](uint64_t g) {
+          L.rng.init(g);
           L.st = VS_EMIT;
-        }
-        chunk_base += take;
-        chunk_left -= take;
-        need = __ballot(L.st == VS_FETCH);
-      }
-      if (__ballot(L.st != VS_IDLE) == 0) break;
-    }
+        }))
+      break;
 
     // ---- walk: one piece (one iteration of update_grids) per walking lane ------------------
     bool leg_end = false;  // the leg's last piece was walked: detectors
@@ -151,14 +92,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
       uint32_t lab = 0;
       if (entered) lab = labels[lin(K, L.xcell, L.ycell, L.zcell)];
       dep = dep && pathlen;
-      w_dep += __popcll(__ballot(dep));
-      if (binned) {
-        if (K.bucket_tiles) emit_bucketed(K, C, WB, dep, vox, val, overflow, bstate);
-        else emit_deposits(K, C, W, dep, vox, val, overflow, whist);
-      } else if (dep) {
-        double* const jm = C->jmean;
-        if (jm) atomic_add_nr(jm + vox, val);
-      }
+      D.file(K, C, dep, vox, val);
       if (walk) {
         if (L.fault) {  // an error stop of the crossing, or the MAX_DDA_ITERS cap: it ends where it stood
           L.old = stood;
@@ -197,43 +131,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
       LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, start, L.dir, pointsep(end, start), L.layer, L.weight);
     }
 
-    // ---- events: rare and expensive, run together (transport_kernel's P7 rule) -------------
+    // ---- events: rare and expensive, run together (events_due, lanekit.h) --------------------
     {
       const bool ev = L.st == VS_EMIT || L.st == VS_FLIGHT || L.st == VS_FRESNEL || L.st == VS_INTERACT || L.st == VS_DONE;
-      const uint64_t evm = __ballot(ev);
-      const uint64_t busy = __ballot(L.st != VS_IDLE && L.st != VS_FETCH);
-      const uint32_t nev = __popcll(evm);
-      if (nev && (nev >= SMCRT_EVENT_LANES || evm == busy)) {
-        if (L.st == VS_INTERACT) {  // kernelsMod.f90:1958-1975 / 2036-2065
-          if (++LU(LU_INTER) > (uint32_t)MAX_INTERACTIONS) {
-            L.fault = true; L.st = VS_DONE;
-          } else {
-            const double ran = L.rng.next(K.key0, K.key1);
-            const TopProps pr = props[L.layer - 1];
-            bool sc = false;
-            if (survival) {
-              const double w_abs = L.weight * (1.0 - pr.albedo);
-              L.weight = L.weight - w_abs;
-              add_cell(K, C->absorb, L, w_abs);
-              sc = true;
-              if (L.weight < 0.01) {
-                if (ran < 0.1) L.weight = L.weight / 0.1;
-                else { LU(LU_STATUS) = 1; LCTR(LC_ABSORBED)++; sc = false; }
-              }
-            } else if (ran < pr.albedo) {
-              sc = true;
-            } else {
-              LU(LU_STATUS) = 1; LCTR(LC_ABSORBED)++;
-              add_cell(K, C->absorb, L, 1.0);
-            }
-            if (sc) {
-              scatter(K, L, pr.hgg);
-              ++LU(LU_NSCATT);
-              LCTR(LC_SCATTERS)++;
-            }
-            L.st = (sc && !L.fault) ? VS_FLIGHT : VS_DONE;
-          }
-        }
+      if (events_due(ev, L.st != VS_IDLE && L.st != VS_FETCH)) {
+        if (L.st == VS_INTERACT) L.st = interact_event(K, C, L, sh, props, survival) ? VS_FLIGHT : VS_DONE;
         if (L.st == VS_FRESNEL) {
           // The crossed axis is the one update_pos snapped (inttau2.f90:538-582: the first of x, y, z
           // with ldir set), handed out by the crossing; its wall is the face of the voxel left that
@@ -250,8 +152,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
             LCTR(LC_FRES)++;
             const double Rf = fresnel(L.dir, N, n1, n2);
             if (L.rng.next(K.key0, K.key1) <= Rf) {  // reflect, surfaces.f90:42-55
-              const double s2 = 2.0 * dot(N, L.dir);
-              L.dir = L.dir - smul(s2, N);
+              L.dir = reflect_dir(L.dir, N);
               // back on the side it came from: the wall minus the signed delta, the crossed axis'
               // cell index as it was
               const int32_t pc_a = L.old_layer, k = pos_a ? pc_a : pc_a - 1;
@@ -259,19 +160,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
               if (ax) { L.old.x = face<GM>(xf, k, K.fex) + back; L.xcell = pc_a; }
               if (ay) { L.old.y = face<GM>(yf, k, K.fey) + back; L.ycell = pc_a; }
               if (az) { L.old.z = face<GM>(zf, k, K.fez) + back; L.zcell = pc_a; }
-              LCTR(LC_REFL)++;
-              if (++LU(LU_BOUNCES) > 1000) {  // a lossless trap never ends otherwise (deviation)
-                LCTR(LC_BABORT)++;
-                L.fault = true; L.st = VS_DONE;
-              }
+              if (!count_bounce(L, sh)) L.st = VS_DONE;
             } else {  // refract, surfaces.f90:57-84
-              const double eta = n1 / n2;
-              V3 Nt = N;
-              double c1 = dot(Nt, L.dir);
-              if (c1 < 0.0) c1 = -c1;
-              else Nt = smul(-1.0, N);
-              const double c2 = sqrt(1.0 - (eta * eta) * (1.0 - c1 * c1));
-              L.dir = smul(eta, L.dir) + smul(eta * c1 - c2, Nt);
+              L.dir = refract_dir(L.dir, N, n1, n2);
               L.layer = L.new_layer;
             }
             if (L.st == VS_FRESNEL) {  // the next leg of the same flight
@@ -281,28 +172,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
             }
           }
         }
-        if (L.st == VS_EMIT) {  // kernelsMod.f90:1937-1945
-          L.fault = false; L.layer = 0;
-          LU(LU_STATUS) = 0; LU(LU_NSCATT) = 0; LU(LU_INTER) = 0; LU(LU_BOUNCES) = 0;
-          L.xcell = L.ycell = L.zcell = 0;
-          emit<GM, XSRC>(K, C, L, 0u);
-          int64_t tries = 0;
-          while (cell_out(K, L)) {
-            if (++tries > MAX_EMIT_TRIES) { L.fault = true; break; }
-            LCTR(LC_RETRIES)++;
-            emit<GM, XSRC>(K, C, L, 0u);
-          }
-          L.tflag = false;
+        if (L.st == VS_EMIT) {
+          const bool ok = emit_event<GM, XSRC>(K, C, L, sh);
           // the position is carried in corner coordinates from here on
           L.old = v3(L.pos.x + K.xmax, L.pos.y + K.ymax, L.pos.z + K.zmax);
-          if (L.fault) {
-            L.layer = 0;  // (no start cell, so no medium)
-            L.st = VS_DONE;
-          } else {
-            if (K.flags & SMCRT_FLAG_RENDER_SOURCE) add_cell(K, C->emission, L, 1.0);
-            L.layer = (int32_t)labels[lin(K, L.xcell, L.ycell, L.zcell)] + 1;
-            L.st = VS_FLIGHT;
-          }
+          if (ok) L.layer = (int32_t)labels[lin(K, L.xcell, L.ycell, L.zcell)] + 1;
+          L.st = ok ? VS_FLIGHT : VS_DONE;  // (a faulted emission has no start cell, so no medium)
         }
         if (L.st == VS_FLIGHT) {
           LCTR(LC_TAU)++;
@@ -314,24 +189,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
           L.st = VS_WALK;
         }
         if (L.st == VS_DONE) {  // photon finished
-          if (L.fault) { LU(LU_STATUS) = 3; LCTR(LC_FAULTS)++; }
-          else if (LU(LU_STATUS) == 0) { LU(LU_STATUS) = 2; LCTR(LC_ESCAPED)++; }
-          LCTR(LC_PHOTONS)++;
-          LCTR(LC_DRAWS) += L.rng.draws;
-          smcrt_photon_record* const records = C->records;
-          if ((K.flags & SMCRT_FLAG_RECORD_PHOTONS) && records) {
-            const uint64_t pid = ((uint64_t)L.rng.pid_hi << 32) | L.rng.pid_lo;
-            smcrt_photon_record* r = records + (pid - C->first_photon);
-            r->pos[0] = L.old.x - K.xmax; r->pos[1] = L.old.y - K.ymax; r->pos[2] = L.old.z - K.zmax;
-            r->dir[0] = L.dir.x; r->dir[1] = L.dir.y; r->dir[2] = L.dir.z;
-            r->weight = L.weight;
-            r->cell[0] = L.xcell; r->cell[1] = L.ycell; r->cell[2] = L.zcell;
-            r->layer = L.layer;
-            r->nscatt = LU(LU_NSCATT);
-            r->bounces = LU(LU_BOUNCES);
-            r->draws = L.rng.draws;
-            r->status = LU(LU_STATUS);
-          }
+          close_photon(L, sh);
+          write_record(K, C, L, sh, v3(L.old.x - K.xmax, L.old.y - K.ymax, L.old.z - K.zmax));
           L.tflag = false; L.fault = false;
           L.st = VS_FETCH;
         }
@@ -339,47 +198,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
     }
   }
 
-  if (binned) {
-    if (K.bucket_tiles) {
-      close_buckets(K, C, WB, w_dep - overflow, overflow);
-      __syncthreads();  // every wave of the block is done depositing
-      close_block_buckets(K, C, bstate);
-    } else {
-      close_log(K, C, W, overflow, whist);
-    }
-  }
-
-  // ---- per-wave counter reduction ------------------------------------------------------
-  unsigned long long* const counters = C->counters;
-  if (counters) {
-    uint32_t c[SMCRT_NCOUNTERS];
-    c[SMCRT_CTR_PHOTONS] = LCTR(LC_PHOTONS);
-    c[SMCRT_CTR_EMIT_RETRIES] = LCTR(LC_RETRIES);
-    c[SMCRT_CTR_SCATTERS] = LCTR(LC_SCATTERS);
-    c[SMCRT_CTR_ABSORBED] = LCTR(LC_ABSORBED);
-    c[SMCRT_CTR_SDF_EVALS] = 0u;
-    c[SMCRT_CTR_DEPOSITS] = lane_id == 0 ? w_dep : 0u;
-    c[SMCRT_CTR_GRID_UPDATES] = LCTR(LC_UPD);
-    c[SMCRT_CTR_TAUINT] = LCTR(LC_TAU);
-    c[SMCRT_CTR_FRESNEL] = LCTR(LC_FRES);
-    c[SMCRT_CTR_REFLECTIONS] = LCTR(LC_REFL);
-    c[SMCRT_CTR_BOUNCE_ABORTS] = LCTR(LC_BABORT);
-    c[SMCRT_CTR_FAULTS] = LCTR(LC_FAULTS);
-    c[SMCRT_CTR_RNG_DRAWS] = LCTR(LC_DRAWS);
-    c[SMCRT_CTR_DETECTOR_HITS] = LCTR(LC_HITS);
-    c[SMCRT_CTR_ESCAPED] = LCTR(LC_ESCAPED);
-    c[SMCRT_CTR_WAVE_ITERS] = lane_id == 0 ? w_iters : 0u;
-#pragma unroll
-    for (int i = 0; i < SMCRT_NCOUNTERS; ++i) {
-      const uint32_t s = wave_sum_u32(c[i]);
-      if (lane_id == 0 && s) atomicAdd(counters + i, (unsigned long long)s);
-    }
-  }
-  double* const nscatt = C->nscatt;
-  if (nscatt) {
-    const uint32_t s = wave_sum_u32(LCTR(LC_SCATTERS));
-    if (lane_id == 0 && s) atomic_add_nr(nscatt, (double)s);
-  }
+  D.close(K, C);
+  flush_counters(C, sh, lane_id, D.w_dep, w_iters);
 }
 
 }  // namespace smcrt

@@ -1103,19 +1103,12 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             const double Rf = fresnel(dir0, N, n1, n2);
             V3 dn;
             if (rg.next(K.key0, K.key1) <= Rf) {  // reflect :42-55, :304-316
-              const double s2 = 2.0 * dot(N, dir0);
-              dn = dir0 - smul(s2, N);
+              dn = reflect_dir(dir0, N);
               ws_count(sh, LC_REFL);
               res = EV_FR_REFLECT;
             } else {  // refract :57-84 (pos = smallStepPos on the incoming direction, in the slot)
               sh->seg[es][SG_DX][o] = ssp.x; sh->seg[es][SG_DY][o] = ssp.y; sh->seg[es][SG_DZ][o] = ssp.z;
-              const double eta = n1 / n2;
-              V3 Nt = N;
-              double c1 = dot(Nt, dir0);
-              if (c1 < 0.0) c1 = -c1;
-              else Nt = smul(-1.0, N);
-              const double c2 = sqrt(1.0 - (eta * eta) * (1.0 - c1 * c1));
-              dn = smul(eta, dir0) + smul(eta * c1 - c2, Nt);
+              dn = refract_dir(dir0, N, n1, n2);
             }
             sh->ev_dir[0][o] = dn.x; sh->ev_dir[1][o] = dn.y; sh->ev_dir[2][o] = dn.z;
           }

@@ -105,6 +105,14 @@ def test_photon_counts(n):
     assert cpu.counter("photons") == n
 
 
+def test_photon_index_above_32_bits():
+    """One lane past a wave, from an index with a high word: the generator's seed and the record's
+    slot (index - first_photon) both take the whole 64-bit index."""
+    gpu, cpu = both(M.cube_scene(), M.grid16(), face_source(), 65, first=2 ** 40 + 7)
+    compare(gpu, cpu)
+    assert cpu.counter("photons") == 65 and cpu.counter("faults") == 0
+
+
 def test_first_photon_and_accumulation():
     """A non-zero first_photon; two runs accumulating into one Result are the run of both."""
     ms, g, src = M.sphere_scene(1), M.grid16(), scene.point_source(INSIDE)

@@ -69,6 +69,15 @@ def test_wave_edges(n):
     assert cpu.counter("photons") == n
 
 
+def test_photon_index_above_32_bits():
+    """One lane past a wave, from an index with a high word: the generator's seed and the record's
+    slot (index - first_photon) both take the whole 64-bit index."""
+    vs, g, src = pattern_case(2)
+    gpu, cpu = both(vs, g, src, 65, first=2 ** 40 + 7)
+    compare(gpu, cpu)
+    assert cpu.counter("photons") == 65 and cpu.counter("faults") == 0
+
+
 def test_rays_through_voxel_edges():
     """Pencils along a face diagonal from a point with x == y: every crossing of an x wall ties
     with a y wall, and after it the photon stands within an ulp of the edge it passed. The
