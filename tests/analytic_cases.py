@@ -1,7 +1,9 @@
 """Test infrastructure only: the scenes of DESIGN.md §3.5 in their three forms (SDF, voxel, mesh),
 their closed-form expectations (tests/analytic_ref.py) and the statistics that compare a run with
-them. Shared by tests/test_analytic_cpu.py and tests/test_gpu_analytic.py; imports neither the
-engine nor the restatements, so that what is compared with what stays in the tests.
+them. Shared by tests/test_analytic_cpu.py and tests/test_gpu_analytic.py, and for the detector
+cases (below the grids') by tests/test_detectors_analytic_cpu.py and
+tests/test_gpu_detectors_analytic.py; runs neither the engine nor the restatements, so that what
+is compared with what stays in the tests.
 
 The grid has three different voxel edges (0.25, 0.125, 0.24) and three different counts, so a
 swapped axis or stride cannot pass; the slab's planes z = +-0.48 are voxel faces.
@@ -325,3 +327,306 @@ def check_c(st):
     assert st["faults"] == 0, st
     assert st["n_pooled"] <= C_POOL_CAP * N_VOXELS, st
     check_batches(st)
+
+
+# ----------------------------------------------------------------------- detector cases ----
+# The detector bins of the same scenes against tests/analytic_ref.py. A photon of
+# scenes A and B meets one detector at most once, so a detector's bins are multinomial counts and
+# its total is binomial.
+def _unit(v):
+    ln = math.sqrt(sum(c * c for c in v))
+    return tuple(c / ln for c in v)
+
+
+def _inside_grid(points, slack=0.0):
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    return bool(np.all(np.abs(p) < np.array(HALF) - slack))
+
+
+def _disc_inside_grid(centre, normal, radius):
+    """The disc's extent along axis a is radius * sqrt(1 - n_a^2)."""
+    n = np.array(_unit(normal))
+    return bool(np.all(np.abs(np.array(centre)) + radius * np.sqrt(1.0 - n * n) < np.array(HALF)))
+
+
+# D-A: circle, camera, annulus, fibre, the circle again with its normal flipped. The normal has
+# three different components, the centres are off the source's foot, the planes lie 0.3 to 0.4
+# from A_SRC (exp(-mu s) is about 0.45 there: a missing `t <= pointSep` window doubles the counts).
+DA_NORMAL = _unit((0.3, -0.2, 0.93))
+DA_CENTRE, DA_RADIUS, DA_NBINS = (0.35, -0.11, 0.38), 0.3, 8
+DA_ANN_CENTRE, DA_ANN = (0.15, -0.18, 0.40), (0.1, 0.28, 9)    # r1, r2, nbins
+# the camera: a rectangle below the source whose normal e2 x e1 points away from it; five pixels
+# a side, so that its 25 bins stand before the annulus', the fibre's and the flipped circle's
+DA_CAM_P1, DA_CAM_E1, DA_CAM_E2 = (0.05, -0.15, -0.30), (0.3, -0.025, 0.1), (0.0, 0.4, 0.1)
+DA_CAM_NBINS, DA_CAM_MAXVAL = 4, 0.55
+# the fibre: its axis passes through A_SRC, the front lens 0.3 away, which is off the focus of the
+# front lens (f1 = 0.1): radius-at-the-fibre = a r with a = -0.533, several bins fill and the last
+# takes what the clamp sends there. The radius is negative at the pinhole, the back lens and the
+# fibre, so those three signed limits never bind; the acceptance angle sets r_max = 0.0402.
+DA_FIBRE_AXIS, DA_FIBRE_H, DA_FIBRE_NBINS = _unit((-0.6, 0.5, -0.62)), 0.3, 6
+DA_FIBRE = dict(focal1=0.1, focal2=0.1, f1_aperture=0.05, f2_aperture=0.02, front_offset=0.02, back_offset=0.12,
+                front_to_pin=0.25, pin_to_back=0.1, pin_aperture=0.01, accept_angle=15.0, core_diameter=0.03)
+
+
+def _fibre_pos():
+    """The fibre's `pos`: the front lens is front_offset further along the axis."""
+    return tuple(s + (DA_FIBRE_H - DA_FIBRE["front_offset"]) * a for s, a in zip(A_SRC, DA_FIBRE_AXIS))
+
+
+def _fibre_front():
+    return tuple(s + DA_FIBRE_H * a for s, a in zip(A_SRC, DA_FIBRE_AXIS))
+
+
+def _fibre_f():
+    d = DA_FIBRE
+    return [d["focal1"], d["focal2"], d["f1_aperture"], d["f2_aperture"], d["front_offset"], d["back_offset"],
+            d["front_to_pin"], d["pin_to_back"], d["pin_aperture"], d["accept_angle"], d["core_diameter"]]
+
+
+def dets_a():
+    r1, r2, nb = DA_ANN
+    p1 = np.array(DA_CAM_P1)
+    flipped = tuple(-c for c in DA_NORMAL)
+    assert _disc_inside_grid(DA_CENTRE, DA_NORMAL, DA_RADIUS) and _disc_inside_grid(DA_ANN_CENTRE, DA_NORMAL, r2)
+    assert _disc_inside_grid(_fibre_front(), DA_FIBRE_AXIS, DA_FIBRE["f1_aperture"])
+    assert _inside_grid([p1, p1 + DA_CAM_E1, p1 + DA_CAM_E2, p1 + DA_CAM_E1 + DA_CAM_E2])
+    for c in (DA_CENTRE, DA_ANN_CENTRE):
+        h = sum((a - b) * n for a, b, n in zip(c, A_SRC, DA_NORMAL))
+        off = math.sqrt(sum((a - b) ** 2 for a, b in zip(c, A_SRC)) - h * h)
+        assert 0.3 < h < 0.4 and off > 0.05, (h, off)
+    return [scene.circle_dect(DA_CENTRE, DA_NORMAL, 1, DA_RADIUS, DA_NBINS),
+            scene.camera(DA_CAM_P1, tuple(p1 + DA_CAM_E1), tuple(p1 + DA_CAM_E2), 1, DA_CAM_NBINS, DA_CAM_MAXVAL),
+            scene.annulus_dect(DA_ANN_CENTRE, DA_NORMAL, 1, r1, r2, nb),
+            scene.fibre_dect(_fibre_pos(), DA_FIBRE_AXIS, 1, DA_FIBRE_NBINS, **DA_FIBRE),
+            scene.circle_dect(DA_CENTRE, flipped, 1, DA_RADIUS, DA_NBINS)]
+
+
+@functools.lru_cache(maxsize=None)
+def expected_a(control=None):
+    """The probability per photon of every bin of dets_a(), one array per detector. `control`
+    names a reference that is wrong on purpose (the negative controls only)."""
+    mu = 1.01 * A_MU if control == "mu+1%" else A_MU
+    normal = DA_NORMAL
+    if control == "normal-swapped":
+        normal = (DA_NORMAL[1], DA_NORMAL[0], DA_NORMAL[2])
+    w = DA_RADIUS / DA_NBINS
+    shift = 0.0
+    if control == "centre+0.1w":    # along the line from the source's foot to the centre
+        rel = np.array(DA_CENTRE) - np.array(A_SRC)
+        rel = rel - float(rel @ np.array(DA_NORMAL)) * np.array(DA_NORMAL)
+        shift = 0.1 * w * rel / math.sqrt(float(rel @ rel))
+    windowed = control != "no-window"
+    ce = AR.circle_edges(DA_RADIUS, DA_NBINS)
+    r1, r2, nb = DA_ANN
+    ae = AR.annulus_edges(r1, r2, nb)
+    if control == "floor":          # int(r / w) + 1: every edge half a bin further out
+        ce = np.concatenate([[0.0], (np.arange(DA_NBINS) + 1.0) * w])
+        ae = r1 + np.concatenate([[0.0], (np.arange(nb) + 1.0) * (r2 - r1) / nb])
+    circle = AR.point_source_disc_bins(A_SRC, mu, np.array(DA_CENTRE) + shift, normal, ce, windowed=windowed)
+    if control == "floor":
+        circle, ann_tail = np.append(circle, 0.0), [0.0]
+    else:
+        ann_tail = []
+    if control == "no-clamp":       # nint(r / w) + 1 beyond the array: the last half bin is lost
+        circle = np.append(circle[:-1], 0.0)
+    annulus = np.append(AR.point_source_disc_bins(A_SRC, mu, np.array(DA_ANN_CENTRE) + shift, normal, ae, windowed=windowed), ann_tail)
+    if control == "annulus-shifted":  # r1 <= r < r2 read as one bin further in
+        annulus = np.append(annulus[1:], 0.0)
+    # the camera neither looks at the leg's length nor at the side it is met from: mu = 0
+    p_cam, xy = AR.point_source_rect(A_SRC, 0.0, DA_CAM_P1, DA_CAM_E1, DA_CAM_E2)
+    cam = np.zeros((DA_CAM_NBINS + 1) ** 2)
+    cam[AR.camera_pixel(xy, DA_CAM_NBINS, DA_CAM_MAXVAL)] = p_cam
+    fibre, r_max, a, _ = AR.fibre_bins(A_SRC, mu, _fibre_front(), DA_FIBRE_AXIS, _fibre_f(), DA_FIBRE_NBINS,
+                                       abs_at_pinhole=control == "fibre-abs-pinhole")
+    if control is None:
+        assert a < -0.1 and np.count_nonzero(fibre) > 2, (a, fibre)
+    flipped = circle.copy() if control == "orientation-ignored" else np.zeros_like(circle)
+    return [circle, cam, annulus, fibre, flipped]
+
+
+# D-B: four circles on the beam's planes. +z: the reflected beam and the light leaving the slab
+# upwards, 2e-3 above the upper face (the first steps after a crossing) and at z = 1.0; -z: what
+# leaves downwards, likewise. The bins are narrower than the distance between successive landings.
+DB_GAP = 2e-3
+DB_DETS = (  # (centre x, y), height above (+) or below (-) the slab's face or None for |z| = 1, radius, nbins
+    ((-0.10, 0.30), +1, DB_GAP, 0.60, 10),
+    ((0.20, 0.45), +1, None, 0.56, 7),
+    ((0.20, 0.45), -1, DB_GAP, 0.60, 10),
+    ((0.25, 0.40), -1, None, 0.50, 10),
+)
+
+
+def _db_geometry(form):
+    out = []
+    for (x, y), side, gap, radius, nb in DB_DETS:
+        z = side * (z_half(form) + gap) if gap is not None else side * 1.0
+        assert np.min(np.abs(AR.faces(NZ, HALF[2]) - z)) > 1e-3, "a detector on a voxel face"
+        out.append(((x, y, z), (0.0, 0.0, float(side)), radius, nb))
+    return out
+
+
+def dets_b(form):
+    return [scene.circle_dect(c, n, 1, radius, nb) for c, n, radius, nb in _db_geometry(form)]
+
+
+@functools.lru_cache(maxsize=None)
+def expected_b(form, control=None):
+    """(p per detector, landings per detector) of dets_b(form)."""
+    mu = 1.01 * B_MU if control == "mu+1%" else B_MU
+    legs = AR.beam_slab_legs(*faces(), B_ORIGIN, B_DIR, z_half(form), B_N_IN, mu_in=mu)
+    ps, lands = [], []
+    for c, n, radius, nb in _db_geometry(form):
+        if control == "orientation-ignored":
+            n = tuple(-v for v in n)
+        p, landed = AR.legs_on_disc(legs, mu, c, n, AR.circle_edges(radius, nb))
+        assert _inside_grid([at for _, _, at, _ in landed], slack=1e-3)
+        ps.append(p)
+        lands.append(landed)
+    return ps, lands
+
+
+# D-C: no closed form in a scattering scene, but an identity: on one plane inside the slab a
+# circle of radius R, one of radius r1 and the annulus r1 < r <= R, each with a single bin.
+DC_CENTRE, DC_NORMAL, DC_R1, DC_R = (0.05, 0.0, 0.30), DA_NORMAL, 0.08, 0.15
+
+
+def dets_c():
+    assert abs(DC_CENTRE[2]) + DC_R < Z_HALF - MESH_INSET
+    return [scene.circle_dect(DC_CENTRE, DC_NORMAL, 1, DC_R, 0), scene.circle_dect(DC_CENTRE, DC_NORMAL, 1, DC_R1, 0),
+            scene.annulus_dect(DC_CENTRE, DC_NORMAL, 1, DC_R1, DC_R, 0)]
+
+
+def check_identity(det_bins, ctr, weighted):
+    """total(circle R) == total(circle r1) + total(annulus): exact integers in an analogue run,
+    to rtol 1e-12 where the bins hold fp64 weights added atomically. The detector_hits counter
+    counts bin increments."""
+    big, small, ann = (float(b) for b in det_bins)
+    assert len(det_bins) == 3 and min(big, small, ann) > 0.0, det_bins
+    if weighted:
+        assert abs(big - (small + ann)) <= 1e-12 * big, det_bins
+        assert ctr["detector_hits"] >= big + small + ann
+    else:
+        assert big == small + ann and all(float(b).is_integer() for b in det_bins), det_bins
+        assert ctr["detector_hits"] == big + small + ann, (ctr, det_bins)
+
+
+# D-O: per-origin totals of batched point sources (SDF form only), D-A's circle, annulus and
+# flipped circle. The origins: A_SRC; two more on the near side at other distances; one behind the
+# plane (every total exactly 0); one whose foot on the plane is outside the disc.
+DO_ORIGINS = (A_SRC, (0.30, -0.22, 0.22), (0.12, 0.05, -0.05), (0.45, -0.25, 0.75), (-0.35, 0.30, 0.15))
+
+
+def dets_o():
+    d = dets_a()
+    return [d[0], d[2], d[4]]
+
+
+@functools.lru_cache(maxsize=None)
+def expected_o(origins=DO_ORIGINS):
+    """p[k, d]: the probability that a photon from origin k is counted by detector d."""
+    r1, r2, _ = DA_ANN
+    out = np.zeros((len(origins), 3))
+    for k, o in enumerate(origins):
+        out[k, 0] = AR.point_source_disc_bins(o, A_MU, DA_CENTRE, DA_NORMAL, [0.0, DA_RADIUS])[0]
+        out[k, 1] = AR.point_source_disc_bins(o, A_MU, DA_ANN_CENTRE, DA_NORMAL, [r1, r2])[0]
+        out[k, 2] = AR.point_source_disc_bins(o, A_MU, DA_CENTRE, tuple(-c for c in DA_NORMAL), [0.0, DA_RADIUS])[0]
+    return out
+
+
+# ------------------------------------------------------ detector statistics and assertions ----
+def evaluate_det(bins, expected, n, hits=None):
+    """Detector bins (one array per detector) of n photons against their probabilities. ALPHA is
+    shared equally by the statistics of the test: for each detector with a support max |z| and
+    sum z^2 of its bins (count_stats, bins below MIN_EVENTS pooled) and the binomial of its total."""
+    live = [d for d, p in enumerate(expected) if p.sum() > 0.0]
+    a = ALPHA / (3.0 * max(1, len(live)))
+    out = {"n": n, "z_bound": binomial_bound(a), "dets": [], "hits": hits,
+           "sum_bins": float(sum(np.asarray(b).sum() for b in bins))}
+    for d, (b, p) in enumerate(zip(bins, expected)):
+        b = np.asarray(b, dtype=np.float64)
+        assert b.shape == p.shape, (d, b.shape, p.shape)
+        st = {"off_support": float(b[p == 0.0].sum()), "total": float(b.sum()), "p_total": float(p.sum()),
+              "integers": bool(np.all(b == np.floor(b)))}
+        if d in live:
+            st["counts"] = count_stats(b, p, n, 2.0 * a)
+            st["z_total"] = binomial_z(b.sum(), p.sum(), n)
+        out["dets"].append(st)
+    return out
+
+
+def check_det(st, pool_cap=None):
+    for d in st["dets"]:
+        assert d["off_support"] == 0.0 and d["integers"], d
+        if "counts" in d:
+            check_counts(d["counts"])
+            assert abs(d["z_total"]) <= st["z_bound"], (d, st["z_bound"])
+            if pool_cap is not None:
+                assert d["counts"]["pooled_share"] <= pool_cap, d
+    if st["hits"] is not None:
+        assert st["hits"] == st["sum_bins"], st
+
+
+def evaluate_origins(totals, expected, n):
+    """totals[k, d] of n photons per origin against p[k, d]: one binomial each, ALPHA shared by
+    those with p > 0; the others must read exactly zero."""
+    t, p = np.asarray(totals, dtype=np.float64), np.asarray(expected)
+    assert t.shape == p.shape, (t.shape, p.shape)
+    live = p > 0.0
+    z = np.zeros_like(p)
+    z[live] = (t[live] - n * p[live]) / np.sqrt(n * p[live] * (1.0 - p[live]))
+    return {"z": z, "max_z": float(np.abs(z).max()), "z_bound": binomial_bound(ALPHA / max(1, int(live.sum()))),
+            "off_support": float(t[~live].sum()), "min_events": float((n * p[live]).min())}
+
+
+def check_origins(st):
+    assert st["off_support"] == 0.0, st
+    assert st["min_events"] >= MIN_EVENTS, st
+    assert st["max_z"] <= st["z_bound"], st
+
+
+def digest(bins):
+    """An exact fingerprint of integer bins: (sum, sum of (i + 1) * bins[i]) over all detectors'
+    bins in order; both are exact in fp64 far beyond the counts used here."""
+    b = np.concatenate([np.asarray(x, dtype=np.float64).ravel() for x in bins])
+    return float(b.sum()), float((b * (np.arange(len(b)) + 1.0)).sum())
+
+
+# The GPU tests' photon counts; the reference's quadrature error is judged at N_GPU.
+N_GPU = 20_000_000    # D-A and D-B, per path
+N_GPU_C = 2_000_000   # D-C is an identity: no bin needs a count
+N_GPU_O = 4_000_000   # per origin, five origins
+N_GPU_E = 2_000_000   # per launch cell, eight cells
+ESCAPE_GRID = ("none", (2, 2, 2), (0.2, 0.2, 0.8), (0.2, -0.1, 0.1))  # symmetry, cells, half-extents, position
+
+
+def escape_case():
+    """(config, launch-cell indices (k, 3) 0-based, p[k, d]) of the escape check: a 2 x 2 x 2
+    symmetry grid without symmetry, its lower four cells before the detectors' planes and its
+    upper four behind them."""
+    from rsmcrt_amd import escape
+    cfg = escape.escape_config(*ESCAPE_GRID[:3], position=ESCAPE_GRID[3])
+    idx, pos = escape.cells(cfg)
+    assert len(idx) == 8 and _inside_grid(pos)
+    return cfg, idx - 1, expected_o(tuple(tuple(float(c) for c in p) for p in pos))
+
+
+def check_escape(es, n):
+    """escape_sym[d, cell] = total / N in fp32 against the binomial of p there."""
+    _, idx, p = escape_case()
+    tot = np.array([[float(es[d, i, j, k]) * n for d in range(3)] for i, j, k in idx])
+    assert np.abs(tot - np.round(tot)).max() < 0.2, tot   # (fp32 of total / N: 6e-8 of the total)
+    st = evaluate_origins(np.round(tot), p, n)
+    print(st)
+    check_origins(st)
+    assert np.count_nonzero(p[:, 0]) == 4 and np.count_nonzero(tot[:, 0]) == 4
+    return st
+
+
+def flat_det(st):
+    """The figures of evaluate_det that PREDICTED records."""
+    out = {"hits": st["hits"]}
+    for d, s in enumerate(st["dets"]):
+        out[f"total{d}"] = s["total"]
+        if "counts" in s:
+            out[f"max_z{d}"], out[f"chi2{d}"], out[f"z_total{d}"] = s["counts"]["max_z"], s["counts"]["chi2"], s["z_total"]
+    return out

@@ -7,6 +7,13 @@ Grids are given by their three arrays of voxel faces (`faces(n, half)`), results
   point_source_track   scene A: an isotropic point source in a homogeneous absorber
   point_source_escape  scene A: the probability of leaving the grid unabsorbed
   beam_slab            scene B: a pencil beam through an index-mismatched absorbing slab
+
+and per-bin expectations of the detectors (their hit rules are stated above circle_edges):
+
+  point_source_disc_bins  scene A: the rings of a circle or annulus detector anywhere in space
+  point_source_rect       scene A: a camera's rectangle, and the one pixel its hits go to
+  fibre_bins              scene A: a fibre detector whose axis passes through the source
+  beam_slab_legs, legs_on_disc  scene B: where each leg of the beam lands on a disc
 """
 from __future__ import annotations
 
@@ -198,3 +205,251 @@ def beam_slab(xe, ye, ze, origin, direction, z_half, n_in, mu_in, n_out=1.0, q_m
             t = np.array([eta * d[0], eta * d[1], math.copysign(cos2, d[2])])  # Snell: the tangential part scales
             legs.append((p, t, q * (1.0 - r), not inside))
     return track, p_abs
+
+
+def beam_slab_legs(xe, ye, ze, origin, direction, z_half, n_in, n_out=1.0, mu_in=0.0, q_min=1e-14,
+                   polarisation="unpolarised"):
+    """The legs beam_slab follows, as a list of (origin, direction, q, length, inside): q is the
+    probability that a photon walks this leg at all (the Fresnel choices and the absorption on the
+    legs before it), length its run to the next plane or to the grid's wall, inside whether it lies
+    in the slab (where a photon survives a run s with probability exp(-mu_in s))."""
+    xe, ye, ze = (np.asarray(e, dtype=np.float64) for e in (xe, ye, ze))
+    glo = np.array([xe[0], ye[0], ze[0]])
+    ghi = np.array([xe[-1], ye[-1], ze[-1]])
+    d0 = np.asarray(direction, dtype=np.float64)
+    d0 = d0 / math.sqrt(float(d0 @ d0))
+    o0 = np.asarray(origin, dtype=np.float64)
+    assert abs(o0[2]) != z_half and np.all(o0 > glo) and np.all(o0 < ghi)
+    todo = [(o0, d0, 1.0, abs(o0[2]) < z_half)]
+    out = []
+    while todo:
+        o, d, q, inside = todo.pop()
+        mu = mu_in if inside else 0.0
+        _, s_exit = _clip(glo, ghi, o, d, math.inf)
+        s_exit = float(s_exit)
+        s_plane, z_plane = math.inf, 0.0
+        if d[2] != 0.0:
+            for zp in (-z_half, z_half):
+                s = (zp - o[2]) / d[2]
+                if s > 1e-12 and s < s_plane:
+                    s_plane, z_plane = s, zp
+        out.append((o, d, q, min(s_exit, s_plane), inside))
+        if s_plane >= s_exit:
+            continue
+        q = q * math.exp(-mu * s_plane)
+        if q < q_min:
+            continue
+        p = o + s_plane * d
+        p[2] = z_plane
+        n1, n2 = (n_in, n_out) if inside else (n_out, n_in)
+        r, cos2 = fresnel_unpolarised(abs(d[2]), n1, n2, polarisation)
+        if q * r >= q_min:
+            todo.append((p, np.array([d[0], d[1], -d[2]]), q * r, inside))
+        if cos2 is not None and q * (1.0 - r) >= q_min:
+            eta = n1 / n2
+            todo.append((p, np.array([eta * d[0], eta * d[1], math.copysign(cos2, d[2])]), q * (1.0 - r), not inside))
+    return out
+
+
+# --------------------------------------------------------------------------- detectors ----
+# The hit rules, read from the reference's text (geometryMod.f90:217-270, detector_base.f90:137-235,
+# detectors.f90:147-469). A flight leg from l0 along the unit vector l of length L meets the plane
+# through `centre` with unit normal n at t = dot(centre - l0, n) / dot(n, l).
+#   circle   hit when dot(n, l) > 1e-6 (oriented: only photons going along n), 0 < t <= L and the
+#            landing radius r <= R. Bin nint(r / w) + 1, at most nbins + 1, w = R / nbins: the
+#            nbins + 1 bins have the edges 0, w/2, 3w/2, ..., (nbins - 1/2) w, R, the first and the
+#            last half as wide as the others. nbins = 0: one bin (w = 1 and the clamp).
+#   annulus  "not inside r1, inside r2" with the same plane rule: r1 < r <= r2, binned by r - r1
+#            with w = (r2 - r1) / nbins.
+#   fibre    a circle of the front aperture on the front lens, then a thin-lens chain in (radius,
+#            gradient) with signed comparisons (fibre_bins).
+#   camera   NOT oriented and NOT windowed: t = dot(p1 - l0, n) / dot(l, n) >= 0 and the landing
+#            point strictly inside the rectangle is all check_hit_camera asks (detectors.f90:460-468),
+#            so every leg whose forward ray meets the rectangle counts, whether or not the photon
+#            gets there. record_hit_2D then files the hit, with weight 1, into the pixel of the
+#            leg's START (hit%pos), x = start.z + p1.x, y = start.y + p1.y, int() and not nint(),
+#            out of nbins + 1 pixels per side. That is the reference's behaviour and is kept.
+# The detectors' `layer` field is read by none of these rules.
+
+def _plane_frame(normal):
+    n = np.asarray(normal, dtype=np.float64)
+    n = n / math.sqrt(float(n @ n))
+    a = np.zeros(3)
+    a[int(np.argmin(np.abs(n)))] = 1.0
+    u = np.cross(n, a)
+    u = u / math.sqrt(float(u @ u))
+    return n, u, np.cross(n, u)
+
+
+def circle_edges(radius, nbins):
+    """The edges of a circle detector's nbins + 1 bins (one bin for nbins = 0)."""
+    if nbins == 0:
+        return np.array([0.0, float(radius)])
+    w = float(radius) / nbins
+    return np.concatenate([[0.0], (np.arange(nbins) + 0.5) * w, [float(radius)]])
+
+
+def annulus_edges(r1, r2, nbins):
+    """The edges in r of an annulus detector's nbins + 1 bins: r1 < r <= r2."""
+    return float(r1) + circle_edges(float(r2) - float(r1), nbins)
+
+
+def point_source_disc_bins(src, mu, centre, normal, edges, order=GL_ORDER, panels=16, windowed=True):
+    """Per photon of an isotropic point source at `src` in a homogeneous absorber (mus = 0, mua =
+    mu, wider than the detector's plane is far): the probability of crossing the plane through
+    `centre` along `normal`, before being absorbed, at radius edges[i] < r <= edges[i + 1] from
+    `centre`. With h the height of the plane above the source along the normal and s the distance
+    from the source, that is the integral of h exp(-mu s) / (4 pi s^3) over the ring, here by a
+    tensor Gauss-Legendre rule in polar coordinates about `centre` (`order` points per ring in r,
+    `panels` panels of `order` points in the angle): the centre need not be the source's foot.
+    A plane behind the source (h <= 0) is never crossed along its normal: all zeros.
+    windowed=False drops exp(-mu s) (a negative control: no `t <= pointSep` window)."""
+    edges = np.asarray(edges, dtype=np.float64)
+    n, u, v = _plane_frame(normal)
+    rel = np.asarray(centre, dtype=np.float64) - np.asarray(src, dtype=np.float64)
+    h = float(rel @ n)
+    out = np.zeros(len(edges) - 1)
+    if h <= 0.0:
+        return out
+    cu, cv = float(rel @ u), float(rel @ v)   # the centre, in the plane, from the source's foot
+    x, w = _gl(order)
+    pe = 2.0 * math.pi * np.arange(panels + 1) / panels
+    phi = (pe[:-1, None] + np.diff(pe)[:, None] * x[None, :]).ravel()
+    wphi = (np.diff(pe)[:, None] * w[None, :]).ravel()
+    for i in range(len(out)):
+        r = edges[i] + (edges[i + 1] - edges[i]) * x
+        wr = (edges[i + 1] - edges[i]) * w
+        a = cu + r[:, None] * np.cos(phi)[None, :]
+        b = cv + r[:, None] * np.sin(phi)[None, :]
+        s = np.sqrt(a * a + b * b + h * h)
+        g = h / (4.0 * math.pi * s ** 3)
+        if windowed:
+            g = g * np.exp(-mu * s)
+        out[i] = float(np.einsum("rp,r,p->", g * r[:, None], wr, wphi))
+    return out
+
+
+def point_source_rect(src, mu, p1, e1, e2, order=GL_ORDER):
+    """The integral of |h| exp(-mu s) / (4 pi s^3) over the rectangle p1 + a e1 + b e2, 0 < a, b < 1
+    (e1 and e2 orthogonal), for a point source at `src`: with mu = 0 the share of the source's
+    directions whose ray meets the rectangle (which is what the reference's camera counts, see
+    above), with mu > 0 the probability of getting there unabsorbed. Returns (p, (x, y)): the
+    coordinates record_hit_2D bins a direct hit by, x = src.z + p1.x and y = src.y + p1.y: the
+    pixel comes from the position of the source (the start of the leg), not from where the
+    rectangle is met, so every direct hit lands in one pixel (camera_pixel)."""
+    p1, e1, e2, src = (np.asarray(a, dtype=np.float64) for a in (p1, e1, e2, src))
+    assert abs(float(e1 @ e2)) <= 1e-12 * math.sqrt(float(e1 @ e1) * float(e2 @ e2)), "not a rectangle"
+    nrm = np.cross(e2, e1)
+    area = math.sqrt(float(nrm @ nrm))
+    h = abs(float((p1 - src) @ nrm)) / area
+    x, w = _gl(order)
+    pts = p1[None, None, :] + x[:, None, None] * e1[None, None, :] + x[None, :, None] * e2[None, None, :] - src
+    s = np.sqrt((pts * pts).sum(axis=-1))
+    g = h * np.exp(-mu * s) / (4.0 * math.pi * s ** 3)
+    return float(np.einsum("ab,a,b->", g, w, w)) * area, (float(src[2] + p1[0]), float(src[1] + p1[1]))
+
+
+def camera_pixel(xy, nbins, maxval):
+    """The index in a camera's (nbins + 1)^2 block of the pixel record_hit_2D picks for the
+    coordinates xy: int(x / w) + 1 with w = maxval / (nbins + 1), at most nbins + 1, and a value
+    below 1 also goes to nbins + 1; x runs fastest."""
+    nb = int(nbins) + 1
+    w = 1.0 if nbins == 0 else float(maxval) / nb
+    idx = []
+    for c in xy:
+        i = min(int(c / w) + 1, nb)   # int() truncates towards zero, as Fortran's does
+        idx.append(nb if i < 1 else i)
+    return (idx[0] - 1) + nb * (idx[1] - 1)
+
+
+def fibre_chain(r, h, f, abs_at_pinhole=False):
+    """check_hit_fibre's thin-lens chain for a ray that meets the front lens at radius r with the
+    gradient r / h (a source on the axis, h in front of the lens). f: focalLength1, focalLength2,
+    f1Aperture, f2Aperture, frontOffset, backOffset, frontToPinSep, pinToBackSep, pinAperture,
+    acceptAngle (degrees), coreDiameter. Returns (accepted, |radius at the fibre|). The comparisons
+    are signed as in the reference: a ray that has crossed the axis (negative radius) passes every
+    aperture. abs_at_pinhole is a negative control."""
+    f1, f2, ap1, ap2, _, back, to_pin, to_back, pin, accept, core = (float(v) for v in f)
+    if r > ap1:
+        return False, 0.0
+    grad = r / h
+    grad = -r / f1 + grad
+    rad = r + grad * to_pin
+    if (abs(rad) if abs_at_pinhole else rad) > pin:
+        return False, 0.0
+    rad = rad + grad * to_back
+    if rad > ap2:
+        return False, 0.0
+    grad = -rad / f2 + grad
+    rad = rad + grad * back
+    if abs(math.atan(grad)) * 360.0 / (2.0 * math.pi) > accept or rad > core / 2.0:
+        return False, abs(rad)
+    return True, abs(rad)
+
+
+def fibre_bins(src, mu, front, axis, f, nbins, abs_at_pinhole=False, order=GL_ORDER):
+    """A fibre detector whose axis passes through the point source: `front` the centre of the front
+    lens (pos + dir * frontOffset), `axis` its direction, pointing away from the source. Every
+    step of the chain is linear in r, so radius-at-the-fibre = a r and each of the five limits
+    (front aperture, pinhole, back aperture, acceptance angle, core radius) is c_k r <= l_k: with
+    signed comparisons a negative c_k never binds, and the accepted set is 0 <= r <= r_max. The
+    bin is nint(|a| r / w) + 1 with w = core / 2 / nbins, at most nbins + 1. Returns (probability
+    per bin [nbins + 1], r_max, a, the edges in r)."""
+    f = [float(v) for v in f]
+    n, _, _ = _plane_frame(axis)
+    rel = np.asarray(front, dtype=np.float64) - np.asarray(src, dtype=np.float64)
+    h = float(rel @ n)
+    assert h > 0.0 and math.sqrt(float(rel @ rel) - h * h if float(rel @ rel) > h * h else 0.0) < 1e-9, "source off the axis"
+    f1, f2, ap1, ap2, _, back, to_pin, to_back, pin, accept, core = f
+    g1 = 1.0 / h - 1.0 / f1                 # gradient after the front lens, per r
+    c_pin = 1.0 + g1 * to_pin               # radius at the pinhole
+    c_back = c_pin + g1 * to_back           # radius at the back lens
+    g2 = g1 - c_back / f2                   # gradient after the back lens
+    a = c_back + g2 * back                  # radius at the fibre
+    limits = [ap1]
+    for c, lim in ((abs(c_pin) if abs_at_pinhole else c_pin, pin), (c_back, ap2), (a, core / 2.0)):
+        if c > 0.0:
+            limits.append(lim / c)
+    if g2 != 0.0:
+        limits.append(math.tan(accept * 2.0 * math.pi / 360.0) / abs(g2))
+    r_max = min(limits)
+    nb = int(nbins) + 1
+    w = 1.0 if nbins == 0 else core / 2.0 / nbins
+    assert a != 0.0
+    inner = np.concatenate([[0.0], (np.arange(nb - 1) + 0.5) * w / abs(a), [math.inf]]) if nb > 1 else np.array([0.0, math.inf])
+    edges = np.minimum(inner, r_max)
+    p = np.zeros(nb)
+    live = np.flatnonzero(np.diff(edges) > 0.0)
+    p[live] = point_source_disc_bins(src, mu, front, n, edges, order=order)[live]
+    return p, r_max, a, edges
+
+
+def legs_on_disc(legs, mu, centre, normal, edges, margin=1e-6):
+    """A pencil beam's legs (beam_slab_legs) against one circle or annulus with bin edges `edges`:
+    a leg that crosses the plane along the normal within its length lands at one radius. Returns
+    (p per bin, landings): the bin of that radius gets q exp(-mu s) (mu inside the slab, 0
+    outside), every other bin exactly 0; landings lists (bin, probability, landing point, radius).
+    No landing radius may lie within `margin` of a bin edge, where rounding would pick the bin."""
+    edges = np.asarray(edges, dtype=np.float64)
+    n, _, _ = _plane_frame(normal)
+    c = np.asarray(centre, dtype=np.float64)
+    p = np.zeros(len(edges) - 1)
+    landings = []
+    for o, d, q, length, inside in legs:
+        den = float(n @ d)
+        if not den > 1e-6:
+            continue
+        t = float((c - o) @ n) / den
+        assert abs(t) > margin and abs(t - length) > margin, "a leg ends within the margin of the plane"
+        if not 0.0 < t <= length:
+            continue
+        at = o + t * d
+        r = math.sqrt(float((at - c) @ (at - c)))
+        assert np.min(np.abs(edges - r)) > margin, (r, edges)
+        if not edges[0] < r <= edges[-1]:
+            continue
+        b = int(np.searchsorted(edges, r, side="left")) - 1
+        pr = q * math.exp(-(mu if inside else 0.0) * t)
+        p[b] += pr
+        landings.append((b, pr, at, r))
+    return p, landings
