@@ -630,3 +630,264 @@ def flat_det(st):
         if "counts" in s:
             out[f"max_z{d}"], out[f"chi2{d}"], out[f"z_total{d}"] = s["counts"]["max_z"], s["counts"]["chi2"], s["z_total"]
     return out
+
+
+# ------------------------------------------------------------- scattering-medium cases ----
+# One homogeneous scattering medium, effectively infinite, against the exact layer expectations
+# of tests/analytic_ref.py (scatter_cumulative; DESIGN.md §3.5 "Scattering media"). Shared by
+# tests/test_scatter_analytic_cpu.py and tests/test_gpu_scatter_analytic.py.
+#
+# The grid: 64 x 72 x 52 voxels of 0.2 x 0.175 x 0.24 over half-extents (6.4, 6.3, 6.24), three
+# different counts and edges; mut = 10, so the walls are more than 60 mean free paths from every
+# source. Figures from the reference alone (test_scatter_analytic_cpu.test_conditions asserts them):
+#   expected escapes in 2.016e7 photons, by the bound of escape_bound(): at most 1.8e-4 (iso g = 0.8),
+#     1.9e-4 (beam -z, mirror) and 3.2e-4 (beam +z), below 1e-12 for g = 0 and g = -0.5;
+#   layers with N p >= 100 along x, y, z: 21, 25, 19 (iso g = 0.8), 15, 16, 12 (g = 0), 13, 15, 11
+#     (g = -0.5), 21, 23, 17 and 21, 23, 18 (the beams), 21, 24, 19 (mirror); the layers below hold at
+#     most 1.5e-5 of the absorptions;
+#   the reference's error, by doubling the k-range, the k-resolution and L: at most 3.6e-3 of a
+#     layer's standard error at 2.016e7 photons (the beams; 2.1e-3 for the point sources).
+S_NX, S_NY, S_NZ = 64, 72, 52
+S_HALF = (6.4, 6.3, 6.24)
+S_EDGES = tuple(2.0 * h / n for h, n in zip(S_HALF, (S_NX, S_NY, S_NZ)))
+S_MUS, S_MUA = 7.0, 3.0
+S_SRC = (0.087, -0.061, 0.07)        # on no face and no voxel centre
+S_MIRROR_SRC = (0.1, 0.0, 0.12)      # a voxel centre in x and z, a voxel face in y
+S_POOL_CAP = 1e-3
+S_ESCAPE_CAP = 1e-3                  # expected escapes over the whole run
+S_REF_ERR_CAP = 1e-2                 # the reference's error per layer, in standard errors at N_GPU_S
+N_GPU_S = 24 * 840_000
+# case -> (source kind, position, direction or None, g)
+S_CASES = {
+    "iso-g0.8": ("point", S_SRC, None, 0.8),
+    "iso-g0": ("point", S_SRC, None, 0.0),
+    "iso-g-0.5": ("point", S_SRC, None, -0.5),
+    "beam-z-": ("pencil", S_SRC, (0.0, 0.0, -1.0), 0.8),
+    "beam-z+": ("pencil", S_SRC, (0.0, 0.0, 1.0), 0.8),
+    "mirror": ("point", S_MIRROR_SRC, None, 0.8),
+}
+S_MIN_LAYERS = {"iso-g0.8": 16, "beam-z-": 16, "beam-z+": 16, "mirror": 16, "iso-g0": 8, "iso-g-0.5": 8}
+# the reference's quadrature, doubled (the estimate of its error)
+S_DOUBLED = dict(kmax=2.0 * AR.SC_KMAX, panel=0.5 * AR.SC_PANEL, ratio=0.5 * AR.SC_RATIO, l0=2 * AR.SC_L0, lk=2.0 * AR.SC_LK)
+
+
+def grid_s():
+    return scene.grid(S_NX, S_NY, S_NZ, *S_HALF)
+
+
+def faces_s():
+    return AR.faces(S_NX, S_HALF[0]), AR.faces(S_NY, S_HALF[1]), AR.faces(S_NZ, S_HALF[2])
+
+
+def scene_s(case, form):
+    """(scene, source) of a scattering case: the medium fills an SDF box far larger than the grid,
+    an all-zero label volume, or both sides of a mesh box far beyond the grid."""
+    kind, pos, direction, g = S_CASES[case]
+    m = scene.mono(S_MUS, S_MUA, g, 1.0)
+    src = scene.point_source(pos) if kind == "point" else scene.pencil_source(pos, direction)
+    if form == "sdf":
+        return scene.Scene([scene.box((60.0, 60.0, 60.0), m, 1)]), src
+    if form == "voxel":
+        return scene.VoxelScene(np.zeros((S_NX, S_NY, S_NZ), dtype=np.uint8), [m]), src
+    ms = scene.MeshScene([m, m], ambient=1)
+    return ms.add_surface(*builders.box_mesh((-30.0, -30.0, -30.0), (30.0, 30.0, 30.0)), 0, 1), src
+
+
+S_CONTROLS = ("g+1%", "mut+1%", "mua+1%", "mus+1%", "g2=g", "isotropic", "reversed", "x-y-swapped", "x-z-swapped",
+              "y-z-swapped", "source+0.1dx", "source+0.1dy", "source+0.1dz")
+
+
+@functools.lru_cache(maxsize=None)
+def reference_s(case, control=None, doubled=False):
+    """The absorption probability per photon of every voxel layer along x, y and z: three arrays.
+    The expected track per photon is that over S_MUA. `control` names a reference that is wrong
+    on purpose (the negative controls only); `doubled` doubles the quadrature's parameters."""
+    kind, pos, direction, g = S_CASES[case]
+    mus, mua = S_MUS, S_MUA
+    pos = list(pos)
+    if control == "g+1%":
+        g = 1.01 * g
+    elif control == "mut+1%":     # the albedo as it is
+        mus, mua = 1.01 * mus, 1.01 * mua
+    elif control == "mua+1%":
+        mua = 1.01 * mua
+    elif control == "mus+1%":
+        mus = 1.01 * mus
+    elif control == "isotropic":
+        g = 0.0
+    elif control == "reversed" and direction is not None:
+        direction = tuple(-c for c in direction)
+    elif control is not None and control.startswith("source+0.1d"):
+        a = "xyz".index(control[-1])
+        pos[a] += 0.1 * S_EDGES[a]
+    elif control is not None and control.endswith("-swapped"):   # the scene with two axes exchanged
+        i, j = "xyz".index(control[0]), "xyz".index(control[2])
+        pos[i], pos[j] = pos[j], pos[i]
+        if direction is not None:
+            direction = list(direction)
+            direction[i], direction[j] = direction[j], direction[i]
+    kw = dict(S_DOUBLED) if doubled else {}
+    if control == "g2=g":         # the right mean cosine, the wrong shape
+        g = (g, g)
+    xs = [e - s for e, s in zip(faces_s(), pos)]
+    cum = [None, None, None]
+    # the axes with the same direction cosine of the source share one k-integral
+    for mu0 in ([None] if kind == "point" else sorted({float(c) for c in direction})):
+        axes = [a for a in range(3) if kind == "point" or float(direction[a]) == mu0]
+        c = AR.scatter_cumulative(np.concatenate([xs[a] for a in axes]), mus, mua, g, mu0, **kw)
+        for a, part in zip(axes, np.split(c, np.cumsum([len(xs[a]) for a in axes])[:-1])):
+            cum[a] = part
+    return [np.maximum(np.diff(c), 0.0) for c in cum]   # (the far layers: 1e-9 of either sign)
+
+
+def escape_bound(case):
+    """A bound on the expected escapes per photon, from the reference alone: a photon that crosses
+    a wall outward flies straight to its next collision, which lies beyond the wall, and is
+    absorbed there with probability 1 - a; so P(cross) <= P(absorption site beyond the wall) / (1 - a),
+    summed over the six walls, each tail by Chernoff's bound on the moment generating function."""
+    kind, pos, direction, g = S_CASES[case]
+    total = 0.0
+    for a in range(3):
+        mu0 = None if kind == "point" else float(direction[a])
+        for side in (1, -1):
+            total += AR.scatter_tail_bound(S_HALF[a] - side * pos[a], S_MUS, S_MUA, g, mu0, side)
+    return total / (1.0 - S_MUS / (S_MUS + S_MUA))
+
+
+def layer_sums(a):
+    """The sums of a grid (nz, ny, nx) over the voxel layers along x, y and z."""
+    return [a.sum(axis=(0, 1)), a.sum(axis=(0, 2)), a.sum(axis=(1, 2))]
+
+
+def run_layers(run, n_batch, batches=BATCHES, keep_grid=False):
+    """`run(first_photon, n)` -> Result for each of `batches` disjoint photon ranges of one seed,
+    reduced at once: {"ab": per axis [B, layers] of absorb, "jm": the same of jmean, "ctr": summed
+    counters, "grid": absorb summed over the batches (keep_grid) or None}."""
+    ab, jm, ctr, g = [[], [], []], [[], [], []], {}, None
+    for b in range(batches):
+        r = run(b * n_batch, n_batch)
+        for a, (sa, sj) in enumerate(zip(layer_sums(r.absorb.astype(np.float64)), layer_sums(r.jmean.astype(np.float64)))):
+            ab[a].append(sa)
+            jm[a].append(sj)
+        if keep_grid:
+            g = r.absorb.astype(np.float64) if g is None else g + r.absorb
+        for k, v in r.counters_dict().items():
+            ctr[k] = ctr.get(k, 0) + v
+    return {"ab": [np.array(x, dtype=np.float64) for x in ab], "jm": [np.array(x, dtype=np.float64) for x in jm],
+            "ctr": ctr, "grid": g}
+
+
+def evaluate_s(run, n_batch, ref, weighted=False):
+    """A scattering case's run (run_layers) against ref = the three arrays of layer probabilities.
+    ALPHA is shared by seven groups: per axis the absorb layer sums (a multinomial, count_stats;
+    with survival bias they hold weights and are batch means like the tracks) and the batch means
+    of the jmean layer sums (batch_stats; a layer's events are its expected absorptions, each of
+    which left track there), and the `scatters` counter, whose mean per photon is a / (1 - a) and
+    variance a / (1 - a)^2 (the collisions before the absorbing one are geometric). With survival
+    bias no photon ends at a collision, so the counter has no such law and is not tested."""
+    n = n_batch * len(run["ab"][0])
+    a = ALPHA / 7.0
+    ctr = run["ctr"]
+    _, _, s_mean, s_var = AR.scatter_moments(S_MUS, S_MUA, 0.0)
+    st = {"n": n, "weighted": weighted, "axes": [], "z_bound": binomial_bound(a),
+          "z_scatters": (ctr["scatters"] - n * s_mean) / math.sqrt(n * s_var),
+          "absorbed": ctr["absorbed"], "escaped": ctr["escaped"], "faults": ctr.get("faults", 0), "photons": ctr["photons"]}
+    for ab, jm, p in zip(run["ab"], run["jm"], ref):
+        assert ab.shape[1] == len(p) and jm.shape[1] == len(p)
+        counts = batch_stats(ab, n_batch * p, n * p, a) if weighted else count_stats(ab.sum(axis=0), p, n, a)
+        st["axes"].append({"counts": counts, "tracks": batch_stats(jm, n_batch * p / S_MUA, n * p, a),
+                           "own": int(np.count_nonzero(n * p >= MIN_EVENTS))})
+    return st
+
+
+def check_s(st, min_layers=8, pool_cap=S_POOL_CAP):
+    assert st["faults"] == 0 and st["escaped"] == 0 and st["photons"] == st["n"], st
+    if not st["weighted"]:
+        assert st["absorbed"] == st["n"], st
+        assert abs(st["z_scatters"]) <= st["z_bound"], st
+    for ax in st["axes"]:
+        for group in ("counts", "tracks"):
+            assert ax[group]["pooled_share"] <= pool_cap and ax["own"] >= min_layers, ax[group]
+        (check_batches if st["weighted"] else check_counts)(ax["counts"])
+        check_batches(ax["tracks"])
+
+
+def flat_s(st):
+    """The figures of evaluate_s that PREDICTED records."""
+    out = {} if st["weighted"] else {"z_scatters": st["z_scatters"]}
+    for name, ax in zip("xyz", st["axes"]):
+        c, t = ax["counts"], ax["tracks"]
+        if st["weighted"]:
+            out[name + "_ab_max_t"], out[name + "_ab_mean_t2"], out[name + "_ab_t_sum"] = c["max_t"], c["mean_t2"], c["t_sum"]
+        else:
+            out[name + "_max_z"], out[name + "_chi2"] = c["max_z"], c["chi2"]
+        out[name + "_max_t"], out[name + "_mean_t2"], out[name + "_score"], out[name + "_t_sum"] = t["max_t"], t["mean_t2"], t["score"], t["t_sum"]
+    return out
+
+
+# S-mirror: the source on a voxel centre in x and z and on a voxel face in y, so that the grid's
+# voxels fall into mirror orbits (x -> -x, y -> -y, z -> -z about the source) of 8 voxels of one
+# size with equal expectations; 4 or 2 where the orbit lies in the source's x or z layer.
+def mirror_window(counts):
+    """The absorb grid (nz, ny, nx) cut to the largest window that is symmetric about S_MIRROR_SRC."""
+    xe, ye, ze = faces_s()
+    i0 = int(np.searchsorted(xe, S_MIRROR_SRC[0])) - 1
+    jf = int(np.argmin(np.abs(ye - S_MIRROR_SRC[1])))
+    k0 = int(np.searchsorted(ze, S_MIRROR_SRC[2])) - 1
+    assert abs(0.5 * (xe[i0] + xe[i0 + 1]) - S_MIRROR_SRC[0]) < 1e-12 and abs(ye[jf] - S_MIRROR_SRC[1]) < 1e-12
+    assert abs(0.5 * (ze[k0] + ze[k0 + 1]) - S_MIRROR_SRC[2]) < 1e-12
+    for e in (xe, ye, ze):
+        assert np.ptp(np.diff(e)) < 1e-12, "an orbit would mix voxels of different size"
+    rx, ry, rz = min(i0, S_NX - 1 - i0), min(jf, S_NY - jf), min(k0, S_NZ - 1 - k0)
+    return np.asarray(counts, dtype=np.float64)[k0 - rz:k0 + rz + 1, jf - ry:jf + ry, i0 - rx:i0 + rx + 1], (rx, ry, rz)
+
+
+def mirror_stats(counts, alpha=ALPHA):
+    """Homogeneity of every mirror orbit whose members expect at least MIN_EVENTS absorptions
+    (the orbit's total over its size: given the total, the members are equiprobable, so that is
+    their expectation): z_m = (c_m - e) / sqrt(e (1 - 1/m)) and sum (c_m - e)^2 / e, chi^2 with
+    m - 1 degrees of freedom per orbit; and per axis the two halves of the layer sums, pair by pair,
+    z = (c+ - c-) / sqrt(c+ + c-). alpha is shared by the four groups, and in each by max |z| and
+    the chi^2 range."""
+    w, (rx, ry, rz) = mirror_window(counts)
+    stack = np.array([w[::sz, ::sy, ::sx] for sz in (1, -1) for sy in (1, -1) for sx in (1, -1)])
+    stack = stack[:, rz:, ry:, rx:]                       # one octant: every orbit once
+    size = np.full(stack.shape[1:], 8.0)
+    size[0, :, :] /= 2.0                                  # the source's z layer mirrors onto itself
+    size[:, :, 0] /= 2.0
+    e = stack.sum(axis=0) / 8.0                           # (a member that counts twice is there twice)
+    use = e >= MIN_EVENTS
+    d = (stack - e[None])[:, use]
+    chi = float(((d * d / e[use][None]).sum(axis=0) * size[use] / 8.0).sum())
+    dof = int((size[use] - 1.0).sum())
+    z = d / np.sqrt(e[use] * (1.0 - 1.0 / size[use]))[None]
+    a = alpha / 4.0
+    members = int(size[use].sum())
+    out = {"orbits": int(use.sum()), "orbits_of_8": int(np.count_nonzero(size[use] == 8.0)), "members": members,
+           "max_z": float(np.abs(z).max()), "chi2": chi, "dof": dof,
+           "z_bound": float(stats.norm.isf(a / (4.0 * members))),
+           "chi2_lo": float(stats.chi2.ppf(a / 4.0, dof)), "chi2_hi": float(stats.chi2.isf(a / 4.0, dof)), "halves": []}
+    for axis, r, even in ((2, rx, False), (1, ry, True), (0, rz, False)):
+        s = w.sum(axis=tuple(i for i in range(3) if i != axis))
+        lo, hi = (s[:r][::-1], s[r:]) if even else (s[:r][::-1], s[r + 1:])
+        keep = 0.5 * (lo + hi) >= MIN_EVENTS
+        zz = (hi[keep] - lo[keep]) / np.sqrt(hi[keep] + lo[keep])
+        v = len(zz)
+        out["halves"].append({"pairs": v, "max_z": float(np.abs(zz).max()), "chi2": float((zz * zz).sum()),
+                              "z_bound": float(stats.norm.isf(a / (4.0 * v))),
+                              "chi2_lo": float(stats.chi2.ppf(a / 4.0, v)), "chi2_hi": float(stats.chi2.isf(a / 4.0, v))})
+    return out
+
+
+def check_mirror(st, min_orbits=50):
+    assert st["orbits_of_8"] >= min_orbits, st
+    for s in [st] + st["halves"]:
+        assert s["max_z"] <= s["z_bound"], s
+        assert s["chi2_lo"] <= s["chi2"] <= s["chi2_hi"], s
+
+
+def flat_mirror(st):
+    out = {"orbits": st["orbits"], "m_max_z": st["max_z"], "m_chi2": st["chi2"]}
+    for name, h in zip("xyz", st["halves"]):
+        out[name + "_half_chi2"] = h["chi2"]
+    return out

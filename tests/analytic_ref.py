@@ -14,6 +14,13 @@ and per-bin expectations of the detectors (their hit rules are stated above circ
   point_source_rect       scene A: a camera's rectangle, and the one pixel its hits go to
   fibre_bins              scene A: a fibre detector whose axis passes through the source
   beam_slab_legs, legs_on_disc  scene B: where each leg of the beam lands on a disc
+
+and the exact voxel-layer expectations of a homogeneous scattering medium without walls:
+
+  scatter_cumulative, scatter_layers_point, scatter_layers_beam  absorptions per layer along an axis
+  scatter_mgf, scatter_tail_bound   the moment generating function of the absorption site, and
+                                    Chernoff's bound on its tails (for the expected escapes)
+  scatter_moments                   exact second and first moments, scatterings per photon
 """
 from __future__ import annotations
 
@@ -453,3 +460,264 @@ def legs_on_disc(legs, mu, centre, normal, edges, margin=1e-6):
         p[b] += pr
         landings.append((b, pr, at, r))
     return p, landings
+
+
+# ------------------------------------------------------------- scattering medium, layers ----
+# A homogeneous medium (mus, mua, g; Henyey-Greenstein) that is effectively infinite. Project the
+# absorption sites onto a fixed axis n: their density is mua times the scalar flux phi_0(x) of a
+# 1-D plane-geometry transport problem. With mu the direction cosine to n, k the Fourier variable
+# of x (phi(k) = int phi(x) exp(-i k x) dx) and phi_l the Legendre moments of the angular flux,
+#   i k [(l + 1) phi_{l+1} + l phi_{l-1}] / (2 l + 1) + sigma_l phi_l = q_l(k),   l = 0 ... L,
+#   sigma_l = mut - mus g^l   (sigma_0 = mua),
+# a tridiagonal system whose elimination from l = L downwards is
+#   D_L = sigma_L, D_{l-1} = sigma_{l-1} + k^2 c_l / D_l, c_l = l^2 / ((2 l - 1)(2 l + 1)),
+#   u_L = q_L,     u_{l-1} = q_{l-1} - i k l / (2 l - 1) u_l / D_l,        phi_0 = u_0 / D_0:
+# for q_l = delta_l0 the continued fraction 1 / (sigma_0 + k^2 c_1 / (sigma_1 + k^2 c_2 / ...)).
+# 1 / (mut + i k mu) has Legendre moments up to l of a few k / mut, which sets the truncation L.
+# The layer [x1, x2] (coordinates from the source) holds per photon
+#   mua / pi Re int_0^inf phi_0(k) (exp(i k x2) - exp(i k x1)) / (i k) dk
+# absorptions and 1 / mua times that as track length. The uncollided flux decays slowly in k and
+# has a closed form in x: it is taken out of phi_0 and added back per layer. What is left decays
+# as 1 / k or faster but matters up to k of 1e3 to 1e4 next to the source, so the k-integral is
+# Gauss-Legendre panels up to SC_K1 mut and beyond that a Filon rule on geometrically spaced
+# nodes: phi_c(k) / (i k) piecewise linear, integrated against exp(i k x) exactly.
+SC_K1 = 6.0          # in units of mut: the end of the Gauss-Legendre panels
+SC_KMAX = 5.0e2      # in units of mut: the end of the k-integral
+SC_PANEL = 0.1       # in units of mut: one 16-point panel (x up to 100 / mut: 10 radians per panel)
+SC_RATIO = 0.004     # the geometric nodes' spacing, relative to k
+SC_L0, SC_LK = 64, 5.0   # L = SC_L0 + SC_LK k / mut
+
+
+def exp_integral_2(x):
+    """E2(x) = int_1^inf exp(-x t) / t^2 dt for x >= 0: exp(-x) - x E1(x), E1 by its power series
+    up to x = 1 and by the continued fraction (modified Lentz) beyond."""
+    x = np.atleast_1d(np.asarray(x, dtype=np.float64))
+    assert np.all(x >= 0.0)
+    e1 = np.zeros_like(x)
+    small = (x > 0.0) & (x <= 1.0)
+    if small.any():
+        xs = x[small]
+        s, term = np.zeros_like(xs), np.ones_like(xs)
+        for n in range(1, 40):
+            term = term * (-xs) / n
+            s -= term / n
+        e1[small] = -0.5772156649015329 - np.log(xs) + s
+    big = x > 1.0
+    if big.any():
+        xb = x[big]
+        b = xb + 1.0
+        c = np.full_like(xb, 1e300)
+        d = 1.0 / b
+        h = d.copy()
+        for n in range(1, 200):
+            an = -float(n * n)
+            b = b + 2.0
+            d = 1.0 / (an * d + b)
+            c = b + an / c
+            h = h * (c * d)
+        e1[big] = h * np.exp(-xb)
+    return np.exp(-x) - x * e1
+
+
+def _moments(g, lmax):
+    """The Legendre moments g_0 ... g_lmax of the scattering kernel: g^l for Henyey-Greenstein. A
+    tuple (g, g_2) replaces the second moment (a negative control: the right mean cosine, the
+    wrong shape)."""
+    if isinstance(g, tuple):
+        m = float(g[0]) ** np.arange(lmax + 1)
+        m[2] = float(g[1])
+        return m
+    return float(g) ** np.arange(lmax + 1)
+
+
+def _sigma(mus, mua, g, lmax):
+    return (mus + mua) - mus * _moments(g, lmax)
+
+
+def _legendre_at(mu0, lmax):
+    p = np.empty(lmax + 1)
+    p[0] = 1.0
+    if lmax >= 1:
+        p[1] = mu0
+    for l in range(1, lmax):
+        p[l + 1] = ((2 * l + 1) * mu0 * p[l] - l * p[l - 1]) / (l + 1)
+    return p
+
+
+def phi0_point(k, mus, mua, g, lmax):
+    """phi_0(k) of the isotropic point source, q_l = delta_l0, as the continued fraction; k may be
+    imaginary (k = i lam gives the moment generating function E[exp(lam x)] / mua). Returns
+    (phi_0, the smallest denominator met: positive while lam lies below the first pole)."""
+    k2 = np.asarray(k) ** 2
+    sig = _sigma(mus, mua, g, lmax)
+    d = np.full(k2.shape, sig[lmax], dtype=k2.dtype)
+    dmin = np.full(k2.shape, np.inf)
+    for l in range(lmax, 0, -1):
+        d = sig[l - 1] + k2 * (l * l / ((2.0 * l - 1.0) * (2.0 * l + 1.0))) / d
+        dmin = np.minimum(dmin, d.real)
+    return 1.0 / d, dmin
+
+
+def phi0_solve(ik, mus, mua, g, q, lmax):
+    """phi_0 of the tridiagonal system above for the sources q[l] (an array [lmax + 1, len(ik)] or
+    [lmax + 1, 1]); `ik` is i k, or a real -lam for the moment generating function. Returns
+    (phi_0, the smallest real part of a denominator)."""
+    ik = np.asarray(ik)
+    sig = _sigma(mus, mua, g, lmax)
+    k2 = -(ik * ik)
+    d = np.full(ik.shape, sig[lmax], dtype=ik.dtype)
+    u = np.broadcast_to(q[lmax], ik.shape).astype(ik.dtype)
+    dmin = np.full(ik.shape, np.inf)
+    for l in range(lmax, 0, -1):
+        u = q[l - 1] - ik * (l / (2.0 * l - 1.0)) * u / d
+        d = sig[l - 1] + k2 * (l * l / ((2.0 * l - 1.0) * (2.0 * l + 1.0))) / d
+        dmin = np.minimum(dmin, d.real)
+    return u / d, dmin
+
+
+def _beam_q(ik, mus, mua, g, mu0, lmax):
+    """The first-collision source of a pencil beam with direction cosine mu0 to the axis: collisions
+    at x = mu0 s with density mus exp(-mut s), re-emitted with the Henyey-Greenstein kernel about
+    the beam, whose azimuthal average about the axis is sum (2l+1)/(4 pi) g^l P_l(mu) P_l(mu0)."""
+    gl = _moments(g, lmax) * _legendre_at(mu0, lmax)
+    return mus * gl[:, None] / ((mus + mua) + np.asarray(ik)[None, :] * mu0)
+
+
+def _collided(k, mus, mua, g, mu0, l0, lk):
+    """phi_0 minus the uncollided flux at the real k (ascending), L chosen per octave of k."""
+    mut = mus + mua
+    out = np.empty(len(k), dtype=np.complex128)
+    start = 0
+    top = max(2.0 * mut, float(k[0]))
+    while start < len(k):
+        stop = int(np.searchsorted(k, top, side="right"))
+        if stop > start:
+            kk = k[start:stop]
+            lmax = int(l0 + lk * kk[-1] / mut)
+            if mu0 is None:
+                out[start:stop] = phi0_point(kk, mus, mua, g, lmax)[0] - np.arctan(kk / mut) / kk
+            else:
+                ik = 1j * kk
+                out[start:stop] = phi0_solve(ik, mus, mua, g, _beam_q(ik, mus, mua, g, mu0, lmax), lmax)[0]
+        start, top = stop, 2.0 * top
+    return out
+
+
+def _collided_cumulative(x, mus, mua, g, mu0, kmax, panel, ratio, l0, lk):
+    """C(x) = mua / pi Re int_0^K phi_c(k) (exp(i k x) - 1) / (i k) dk for every x: the collided
+    absorptions per photon between the source's plane and x (signed)."""
+    mut = mus + mua
+    x = np.asarray(x, dtype=np.float64)
+    # Gauss-Legendre panels: the integrand is smooth, (exp(i k x) - 1) / (i k) -> x at k = 0
+    k1 = SC_K1 * mut
+    pe = np.linspace(0.0, k1, int(round(SC_K1 / panel)) + 1)
+    gx, gw = _gl(16)
+    k = (pe[:-1, None] + np.diff(pe)[:, None] * gx[None, :]).ravel()
+    w = (np.diff(pe)[:, None] * gw[None, :]).ravel()
+    f = _collided(k, mus, mua, g, mu0, l0, lk)
+    low = ((f * w / (1j * k))[None, :] * np.expm1(1j * k[None, :] * x[:, None])).sum(axis=1)
+    # Filon: F = phi_c / (i k) linear between the nodes, against exp(i k x) and against 1
+    kn = k1 * (1.0 + ratio) ** np.arange(int(math.ceil(math.log(kmax / SC_K1) / math.log1p(ratio))) + 1)
+    fn = _collided(kn, mus, mua, g, mu0, l0, lk) / (1j * kn)
+    h = np.diff(kn)
+    theta = x[:, None] * h[None, :]
+    ok = np.abs(theta) > 1e-2
+    th = np.where(ok, theta, 1.0)
+    e = np.exp(1j * th)
+    a_big = (e - 1.0) / (1j * th)
+    b_big = e / (1j * th) + (e - 1.0) / (th * th)
+    ts = np.where(ok, 0.0, theta)
+    a_small = 1.0 + 0.5j * ts - ts ** 2 / 6.0 - 1j * ts ** 3 / 24.0 + ts ** 4 / 120.0
+    b_small = 0.5 + 1j * ts / 3.0 - ts ** 2 / 8.0 - 1j * ts ** 3 / 30.0 + ts ** 4 / 144.0
+    a, b = np.where(ok, a_big, a_small), np.where(ok, b_big, b_small)
+    seg = np.exp(1j * x[:, None] * kn[None, :-1]) * h[None, :] * (fn[None, :-1] * a + np.diff(fn)[None, :] * b)
+    high = seg.sum(axis=1) - (h * 0.5 * (fn[:-1] + fn[1:])).sum()
+    return mua / math.pi * (low + high).real
+
+
+def _uncollided_point(x, mus, mua):
+    """The uncollided absorptions of the point source between the source's plane and x: the
+    marginal of mua exp(-mut r) / (4 pi r^2) integrated, mua (1 - E2(mut |x|)) / (2 mut), odd."""
+    mut = mus + mua
+    x = np.asarray(x, dtype=np.float64)
+    return np.sign(x) * mua * (1.0 - exp_integral_2(mut * np.abs(x))) / (2.0 * mut)
+
+
+def _uncollided_beam(x, mus, mua, mu0):
+    """The same for the beam: absorptions with density mua exp(-mut s) at x = mu0 s."""
+    mut = mus + mua
+    x = np.asarray(x, dtype=np.float64)
+    if mu0 == 0.0:
+        return np.where(x > 0.0, 0.5, np.where(x < 0.0, -0.5, 0.0)) * mua / mut   # all in the source's plane
+    s = np.maximum(x / mu0, 0.0)
+    return math.copysign(1.0, mu0) * mua / mut * -np.expm1(-mut * s)
+
+
+def scatter_cumulative(x, mus, mua, g, mu0=None, kmax=SC_KMAX, panel=SC_PANEL, ratio=SC_RATIO, l0=SC_L0, lk=SC_LK):
+    """Absorptions per photon between the source's plane and the plane at x (signed, any array of
+    coordinates along the axis measured from the source) in a homogeneous infinite medium, for an
+    isotropic point source (mu0 None) or a pencil beam with direction cosine mu0 to the axis. For
+    mu0 = 0 the uncollided absorptions all lie in the source's plane: no x may be 0 then."""
+    mus, mua = float(mus), float(mua)
+    assert mua > 0.0 and mus >= 0.0 and abs(g[0] if isinstance(g, tuple) else g) < 1.0
+    x = np.asarray(x, dtype=np.float64)
+    if mu0 is None:
+        unc = _uncollided_point(x, mus, mua)
+    else:
+        assert mu0 != 0.0 or np.min(np.abs(x)) > 0.0, "the beam lies in a layer's face"
+        unc = _uncollided_beam(x, mus, mua, float(mu0))
+    if mus == 0.0:
+        return unc
+    return unc + _collided_cumulative(x, mus, mua, g, mu0, kmax * (mus + mua), panel, ratio, l0, lk)
+
+
+def scatter_layers(edges, source, mus, mua, g, mu0=None, **kw):
+    """Absorptions per photon in every layer between successive `edges` (ascending, absolute
+    coordinates along the axis) for a source at the coordinate `source` (scatter_cumulative). The
+    expected track length per photon in a layer is this over mua."""
+    return np.diff(scatter_cumulative(np.asarray(edges, dtype=np.float64) - float(source), mus, mua, g, mu0, **kw))
+
+
+def scatter_layers_point(edges, source, mus, mua, g, **kw):
+    return scatter_layers(edges, source, mus, mua, g, None, **kw)
+
+
+def scatter_layers_beam(edges, source, mus, mua, g, mu0, **kw):
+    return scatter_layers(edges, source, mus, mua, g, float(mu0), **kw)
+
+
+def scatter_mgf(lam, mus, mua, g, mu0=None, lmax=200):
+    """E[exp(lam x)] of the absorption site's coordinate x along the axis (from the source), for
+    real lam below the first pole: mua phi_0(k = i lam), the uncollided part included. Returns
+    (value, valid): valid is False where a denominator of the elimination is not positive."""
+    lam = np.atleast_1d(np.asarray(lam, dtype=np.float64))
+    mut = mus + mua
+    if mu0 is None:
+        v, dmin = phi0_point(1j * lam, mus, mua, g, lmax)
+        v = v.real
+    else:
+        ok = mut - lam * mu0 > 0.0
+        ik = np.where(ok, -lam, 0.0)
+        v, dmin = phi0_solve(ik, mus, mua, g, _beam_q(ik, mus, mua, g, mu0, lmax), lmax)
+        v = v + 1.0 / (mut + ik * mu0)
+        dmin = np.where(ok, dmin, -1.0)
+    return mua * v, dmin > 0.0
+
+
+def scatter_tail_bound(w, mus, mua, g, mu0=None, side=1):
+    """A rigorous bound on P(absorption site beyond x = side * w), w > 0 from the source:
+    Chernoff's min over lam of E[exp(side lam x)] exp(-lam w), on a grid of lam below the pole."""
+    lam = np.linspace(0.0, mus + mua, 4001)[1:]
+    m, valid = scatter_mgf(side * lam, mus, mua, g, mu0)
+    valid = np.cumprod(valid).astype(bool) & (m > 0.0)
+    assert valid.any()
+    return float(np.min(m[valid] * np.exp(-lam[valid] * w)))
+
+
+def scatter_moments(mus, mua, g):
+    """(<x^2> of the point source's absorption sites along any axis, <z> of a beam's along itself,
+    mean and variance of the scatterings per photon)."""
+    mut = mus + mua
+    a = mus / mut
+    return (2.0 / (3.0 * mut * mut * (1.0 - a) * (1.0 - a * g)), 1.0 / (mut * (1.0 - a * g)),
+            a / (1.0 - a), a / (1.0 - a) ** 2)
