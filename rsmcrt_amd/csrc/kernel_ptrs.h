@@ -9,9 +9,11 @@
 // transport of mesh.h), so
 // the instantiations of transport_kernel and ws_kernel (kernels.h, ws.h) build in parallel
 // instead of in one translation unit. Each object exports these getters; hipLaunchKernel and
-// the occupancy queries take the host stubs they return.
+// the occupancy query take the host stub that kernel_ptr returns for a launch choice.
 #pragma once
 #include <stddef.h>
+
+#include "launchchoice.h"
 
 namespace smcrt {
 
@@ -111,6 +113,16 @@ inline const void* ws_kernel_ptr(bool lds_faces, int gm, bool xf, int slots, boo
     default: return kinst_ws_1_2(x, slots, t);
   }
 }
+// the host stub and the block size of a launch choice (sceneplan.h launch_choice)
+inline const void* kernel_ptr(const LaunchChoice& c) {
+  switch (c.family) {
+    case KF_WS: return ws_kernel_ptr(c.lds_faces, c.gm, c.xf, c.slots, c.iv, c.tk);
+    case KF_VOXEL: return voxel_kernel_ptr(c.gm, c.xsrc);
+    case KF_MESH: return mesh_kernel_ptr(c.gm, c.xsrc);
+    default: return transport_kernel_ptr(c.lds_faces, c.gm, c.xsrc, c.coop, c.hist, c.phas);
+  }
+}
+inline int kernel_threads(const LaunchChoice& c) { return c.family == KF_WS ? kinst_ws_threads() : 256; }
 // diagnostic builds: the kernels' tallies summed over the objects (each is cleared)
 inline void kinst_diag_gather(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6) {
   for (int i = 0; i < 72; ++i) d72[i] = 0;

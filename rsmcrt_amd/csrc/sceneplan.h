@@ -17,6 +17,7 @@
 #include "transport.h"  // (before deposit.h, which uses KParams)
 #include "cull.h"
 #include "deposit.h"
+#include "launchchoice.h"
 
 namespace smcrt {
 
@@ -174,10 +175,6 @@ int plan_voxel_scene(const uint8_t* labels, const smcrt_medium* media, int32_t n
 // The host's restatement of vox_of (transport.h) for smcrt_scene_classify on a voxel scene: the
 // 1-based cell of centred coordinate p on an axis of n cells, -1 outside
 int32_t host_vox_of(double p, int32_t n, double max);
-// Dynamic LDS of voxel_kernel (voxel.h): media + faces, then the deposit words
-inline size_t voxel_lds(const ScenePlan& p, uint32_t dep_words) {
-  return p.face_bytes + (size_t)dep_words * sizeof(uint32_t);
-}
 
 // A mesh scene (smcrt_mesh_scene_create): validates (finite vertices, indices in range, no
 // degenerate triangle, media, every surface closed and consistently oriented with one pair of
@@ -191,8 +188,6 @@ int plan_mesh_scene(const double* verts, int32_t nv, const int32_t* tris, const 
 // The medium (0-based) of centred point p of a mesh plan: a host cast along (0, 0, 1) and the
 // emission rule (inside(tri) if dir . N > 0 at the hit, outside(tri) if not, ambient without a hit)
 int32_t mesh_medium_at(const ScenePlan& p, const double pt[3]);
-// Dynamic LDS of mesh_kernel (mesh.h): voxel_kernel's layout
-inline size_t mesh_lds(const ScenePlan& p, uint32_t dep_words) { return voxel_lds(p, dep_words); }
 
 // Field screens (smcrt_scene_set_screens, smcrt_screen_hit): validates smcrt.h's list (1 <= n <= 16,
 // finite numbers, non-zero orthogonal edges, 1 <= nu, nv <= 4096, sides, reserved), naming the
@@ -275,6 +270,44 @@ inline bool launch_lean(bool lean_ok, bool xsrc, uint32_t bucket_tiles, uint32_t
 // ws_kernel's in-voxel segments (ws.h): on by default in the plain instantiation; the XF one
 // (xf: Fresnel interfaces or detectors), which measured slower with them, only when asked for
 inline bool ws_invoxel_on(int knob, bool xf) { return knob < 0 ? !xf : knob != 0; }
+// XF: the scene has Fresnel interfaces or detectors (ws_kernel's instantiation with their program
+// points, and the lane scratch that goes with it)
+inline bool plan_xf(const ScenePlan& p) { return p.fresnel || p.n_dets > 0; }
+
+// ---- the launch choice (launchchoice.h): which compiled kernel a launch runs, and with what LDS ----
+// The choice for one launch of plan p: `xsrc` the general emitter, `bucket_tiles` the launch's
+// KParams::bucket_tiles, `flags` the run's, and the scene state that matters: path tracking and
+// the phasor tally configured, the number of field screens. (`lean_ok` false, or no bucket
+// tiles, never gives ws_kernel: what a scene's transport_kernel grids are sized with.)
+inline LaunchChoice launch_choice(const ScenePlan& p, bool lean_ok, bool xsrc, uint32_t bucket_tiles, uint32_t flags,
+                                  bool path_on, bool phasor_on, size_t n_screens) {
+  LaunchChoice c;
+  c.gm = p.grid_mode;
+  if (p.voxel || p.mesh) {  // (neither has a lean path, a path recorder or a phasor tally)
+    c.family = p.mesh ? KF_MESH : KF_VOXEL;
+    c.xsrc = xsrc;
+    c.lds = p.face_bytes + (size_t)dep_words(p) * sizeof(uint32_t);  // (voxel.h, mesh.h: media + faces, then the deposit words)
+  } else if (launch_lean(lean_ok, xsrc, bucket_tiles, flags)) {
+    c.family = KF_WS;
+    c.lds_faces = p.lds_faces;
+    c.xf = plan_xf(p);
+    c.slots = p.ws_slots;
+    c.iv = ws_invoxel_on(p.ws_invoxel, c.xf);
+    c.tk = (flags & SMCRT_FLAG_TEST_KERNEL) != 0;
+    c.lds = lean_lds(p);
+  } else {
+    c.xsrc = xsrc;
+    c.coop = p.coop_lanes > 0;  // (many tops: the cooperative tail EVAL and culling; it costs registers)
+    c.hist = (flags & SMCRT_FLAG_TRACK_PATHS) && path_on;
+    c.phas = (flags & SMCRT_FLAG_PHASOR) && phasor_on && !c.hist;  // (smcrt_run refuses the two together)
+    c.scr = c.phas && n_screens > 0;
+    // (the general emitter with the COOP machinery, the path recorder and the phasor tally are
+    // instantiated with faces in device memory only: the library's build time; transport_lds follows)
+    c.lds_faces = p.lds_faces && !((xsrc && c.coop) || c.hist || c.phas);
+    c.lds = transport_lds(p, dep_words(p), xsrc, c.hist || c.phas, c.scr);
+  }
+  return c;
+}
 // lean_margin per axis (lean.h, ws.h), with the operations the kernel used to do
 inline void lean_margins(uint32_t lean_debug, const smcrt_grid& g, double lo[3], double hi[3]) {
   const double eps = 1e-8, mf = (lean_debug & 3u) ? 0.0 : 2.0 * eps;

@@ -121,9 +121,7 @@ struct smcrt_scene : ScenePlan {
   DevBuf<smcrt_photon_record> d_records;
   size_t records_cap = 0;
   Stream stream;
-  int grid_blocks = 0;
-  int grid_blocks_x = 0;   // the XSRC (general emitter) instantiation
-  int grid_blocks_ws = 0;  // ws_kernel (ws.h): the lean path with photon, event and walker waves
+  int grid_table[N_GRID_KEYS] = {};  // blocks_for: the persistent grid per LaunchChoice::grid_key(); 0: not asked for yet
   // ws_kernel's lane scratch (ws.h WX_*) for scenes with Fresnel interfaces or detectors: one
   // region per launch stream (queue index), lscratch_stride bytes apart
   DevBuf<char> d_lscratch;
@@ -183,19 +181,16 @@ struct smcrt_scene : ScenePlan {
   DevBuf<smcrt_path> d_path_headers;
   DevBuf<unsigned long long> d_path_ctl;
   uint64_t hist_lanes = 0;
-  int grid_blocks_hist[2] = {0, 0};  // the HIST instantiations' grids (plain, XSRC)
   // the phasor tally (smcrt_scene_set_phasor; phasor.h): the grid, 2 doubles per voxel
   bool phasor_on = false;
   smcrt_phasor_config phasor_cfg{};
   DevBuf<double> d_phasor;
-  int grid_blocks_phas[2] = {0, 0};  // the PHAS instantiations' grids (plain, XSRC)
   // field screens (smcrt_scene_set_screens; screen.h): the table and the field buffer, tallied by
   // phasor launches only; such a launch holds a fourth row of start-point LDS, hence grids of its own
   std::vector<ScreenDev> screens;
   int64_t screen_doubles = 0;
   DevBuf<ScreenDev> d_screens;
   DevBuf<double> d_screen_field;
-  int grid_blocks_phas_scr[2] = {0, 0};
   // the volume source (smcrt_scene_set_volume_source; volsrc.h): the running sums of the weights
   // and what the pick and smcrt_scene_volume_source_info read; d_vs_cdf null: no table
   DevBuf<double> d_vs_cdf;
@@ -225,16 +220,42 @@ static hipError_t harvest_times(smcrt_scene* s) {
   return hipSuccess;
 }
 
-// The transport kernel instantiation for this scene (LDS faces? power-of-two grid?).
-// Scenes with many tops (coop_lanes > 0) get an instantiation with the cooperative tail EVAL
-// and culling; it costs registers (scratch spills), so small scenes never pay for it. With the
-// general emitter (XSRC: other sources, batched origins, composites below the top level) that
-// is transport_kernel<.., true, true> (round 4; before, such scenes ran the serial EVAL).
-static const void* transport_fn(const smcrt_scene* s, bool xsrc, bool hist = false, bool phas = false) {
-  // (the general emitter with the COOP machinery is instantiated with faces in device memory
-  // only: three kernels instead of six, the library's build time, for the rare scenes that run
-  // it; transport_lds follows)
-  return transport_kernel_ptr(s->lds_faces, s->grid_mode, xsrc, s->coop_lanes > 0, hist, phas);
+// The persistent grid of a launch choice: CUs x the blocks of its kernel, block and LDS per CU.
+static int blocks_for(smcrt_scene* s, LaunchChoice c) {
+  int& blocks = s->grid_table[c.grid_key()];
+  if (!blocks) {
+    c.tk = false;  // (the test_kernel instantiation has the same block, LDS and register cap: one grid for both)
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel_ptr(c), kernel_threads(c), c.lds) != hipSuccess ||
+        per_cu < 1)
+      per_cu = 1;
+    blocks = s->n_cus * per_cu;
+  }
+  return blocks;
+}
+// The larger of the scene's plain and XSRC grids of transport_kernel (or voxel_kernel, mesh_kernel):
+// what the pool rules (sceneplan.h pool_slack_records) count as a launch's blocks, for every family.
+static int transport_blocks(smcrt_scene* s) {
+  return std::max(blocks_for(s, launch_choice(*s, false, false, 0, 0, false, false, 0)),
+                  blocks_for(s, launch_choice(*s, false, true, 0, 0, false, false, 0)));
+}
+
+// Wait for the scene's stream, copy the n elements at d to the host and add them into out. Caller holds s->mu.
+template <class T, class U>
+static hipError_t read_add(smcrt_scene* s, const T* d, size_t n, U* out) {
+  std::vector<T> h(n);
+  hipError_t e = hipSetDevice(s->device);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  if (e == hipSuccess) e = hipMemcpy(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost);
+  for (size_t i = 0; e == hipSuccess && i < n; ++i) out[i] += h[i];
+  return e;
+}
+// Wait for the scene's stream and zero the n doubles at d. Caller holds s->mu.
+static int zero_tally(smcrt_scene* s, double* d, size_t n) {
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(hipMemset(d, 0, n * sizeof(double)));
+  return SMCRT_OK;
 }
 
 // ---- the watchdog (transport.h watchdog_expired): d_queue[Q_WATCHDOG] holds the first
@@ -380,45 +401,48 @@ static int create_fold_state(smcrt_scene* s) {
   return SMCRT_OK;
 }
 
-// The persistent grids: blocks per CU of the instantiations the scene runs, and the lean
-// path's lane scratch (without it the scene keeps transport_kernel, which needs none).
+// The grids sized at creation: ws_kernel's, for the lean path's lane scratch (without it the scene
+// keeps transport_kernel, which needs none), and transport_blocks for the pool rules.
 static void size_grids(smcrt_scene* s) {
-  int per_cu = 0, cus = 0;
+  int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess || cus < 1) cus = 256;
   s->n_cus = cus;
   int khz = 0;  // s_memrealtime's rate
   if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, s->device) == hipSuccess && khz > 0) s->wall_khz = khz;
   s->lean_ok = s->lean_candidate;
-  const bool xf = s->fresnel || s->n_dets > 0;
   if (s->lean_ok) {
-    // (the test_kernel instantiation has the same block, LDS and register cap: one grid for both)
-    hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, ws_kernel_ptr(s->lds_faces, s->grid_mode, xf, s->ws_slots, ws_invoxel_on(s->ws_invoxel, xf), false),
-        kinst_ws_threads(), lean_lds(*s));
-    if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-    s->grid_blocks_ws = cus * per_cu;
-    if (xf) {  // the lane scratch, per launch stream
-      s->lscratch_stride = (kinst_ws_scratch_bytes((size_t)s->grid_blocks_ws * kinst_ws_photon_lanes()) + 255) & ~(size_t)255;
+    const int ws_blocks = blocks_for(s, launch_choice(*s, true, false, 1, SMCRT_FLAG_PATHLENGTH, false, false, 0));
+    if (plan_xf(*s)) {  // the lane scratch, per launch stream
+      s->lscratch_stride = (kinst_ws_scratch_bytes((size_t)ws_blocks * kinst_ws_photon_lanes()) + 255) & ~(size_t)255;
       if (s->d_lscratch.alloc(s->lscratch_stride * N_QUEUES) != hipSuccess) {
         (void)hipGetLastError();
         s->lean_ok = false;
       }
     }
   }
-  if (s->verbose)
+  if (s->verbose)  // (the transport grid is sized after this line: it has always read 0)
     std::fprintf(stderr, "[smcrt] scene: lean %d (ws slots %d, blocks/CU %d, static LDS %zu + dynamic %zu B), transport grid %d\n",
-                 (int)s->lean_ok, s->ws_slots, s->grid_blocks_ws / std::max(1, cus), kinst_ws_shared_bytes(s->ws_slots), lean_lds(*s),
-                 s->grid_blocks);
-  for (int x = 0; x < 2; ++x) {
-    hipError_t oe = s->mesh  ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mesh_kernel_ptr(s->grid_mode, x == 1),
-                                                                            256, mesh_lds(*s, dep_words(*s)))
-                    : s->voxel ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, voxel_kernel_ptr(s->grid_mode, x == 1),
-                                                                            256, voxel_lds(*s, dep_words(*s)))
-                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, transport_fn(s, x == 1), 256,
-                                                                            transport_lds(*s, dep_words(*s), x == 1));
-    if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-    (x ? s->grid_blocks_x : s->grid_blocks) = cus * per_cu;
-  }
+                 (int)s->lean_ok, s->ws_slots, s->grid_table[GRID_KEY_WS] / std::max(1, cus), kinst_ws_shared_bytes(s->ws_slots),
+                 lean_lds(*s), s->grid_table[0]);
+  (void)transport_blocks(s);
+}
+
+// What the scene-creation functions share once their planner has succeeded: the device checks, the
+// scene with the plan moved in, the uploads (`upload_kind`: the kind's own), the fold state, the grids.
+static int create_scene(ScenePlan&& plan, int32_t device, int (*upload_kind)(smcrt_scene*), smcrt_scene** out) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMCRT_ERR_NO_DEVICE, "no HIP device");
+  if (device < 0 || device >= ndev) return fail(SMCRT_ERR_INVALID_ARG, "device ordinal out of range");
+  std::unique_ptr<smcrt_scene, void (*)(smcrt_scene*)> s(new smcrt_scene(), smcrt_scene_destroy);
+  static_cast<ScenePlan&>(*s) = std::move(plan);
+  s->device = device;
+  if (hipSetDevice(device) != hipSuccess) return fail(SMCRT_ERR_HIP, "hipSetDevice failed");
+  int st;
+  if ((st = upload_plan(s.get())) || (st = upload_kind(s.get())) || (s->n_tiles && (st = create_fold_state(s.get()))))
+    return st;
+  size_grids(s.get());
+  *out = s.release();
+  return SMCRT_OK;
 }
 
 int smcrt_scene_create(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32_t* top, int32_t n_top,
@@ -429,21 +453,8 @@ int smcrt_scene_create(const smcrt_sdf_node* nodes, int32_t n_nodes, const int32
   *out = nullptr;
   const PlanLimits lim{kinst_ws_shared_bytes(2), kinst_ws_shared_bytes(3)};
   ScenePlan plan;
-  int st = plan_scene(nodes, n_nodes, top, n_top, grid, dets, n_dets, read_knobs(), lim, &plan);
-  if (st) return st;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMCRT_ERR_NO_DEVICE, "no HIP device");
-  if (device < 0 || device >= ndev) return fail(SMCRT_ERR_INVALID_ARG, "device ordinal out of range");
-  std::unique_ptr<smcrt_scene, void (*)(smcrt_scene*)> s(new smcrt_scene(), smcrt_scene_destroy);
-  static_cast<ScenePlan&>(*s) = std::move(plan);
-  s->device = device;
-  if (hipSetDevice(device) != hipSuccess) return fail(SMCRT_ERR_HIP, "hipSetDevice failed");
-  if ((st = upload_plan(s.get())) || (s->cull.enabled && (st = upload_cull(s.get()))) ||
-      (s->n_tiles && (st = create_fold_state(s.get()))))
-    return st;
-  size_grids(s.get());
-  *out = s.release();
-  return SMCRT_OK;
+  if (const int st = plan_scene(nodes, n_nodes, top, n_top, grid, dets, n_dets, read_knobs(), lim, &plan)) return st;
+  return create_scene(std::move(plan), device, [](smcrt_scene* s) { return s->cull.enabled ? upload_cull(s) : SMCRT_OK; }, out);
 }
 
 int smcrt_voxel_scene_create(const uint8_t* labels, const smcrt_medium* media, int32_t n_media, const smcrt_grid* grid,
@@ -452,21 +463,9 @@ int smcrt_voxel_scene_create(const uint8_t* labels, const smcrt_medium* media, i
   if (!out) return fail(SMCRT_ERR_INVALID_ARG, "out is NULL");
   *out = nullptr;
   ScenePlan plan;
-  int st = plan_voxel_scene(labels, media, n_media, grid, dets, n_dets, read_knobs(), &plan);
-  if (st) return st;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMCRT_ERR_NO_DEVICE, "no HIP device");
-  if (device < 0 || device >= ndev) return fail(SMCRT_ERR_INVALID_ARG, "device ordinal out of range");
-  std::unique_ptr<smcrt_scene, void (*)(smcrt_scene*)> s(new smcrt_scene(), smcrt_scene_destroy);
-  static_cast<ScenePlan&>(*s) = std::move(plan);
-  s->device = device;
-  if (hipSetDevice(device) != hipSuccess) return fail(SMCRT_ERR_HIP, "hipSetDevice failed");
-  if ((st = upload_plan(s.get())) || (st = upload(s->d_labels, s->labels.data(), s->labels.size(), "label upload")) ||
-      (s->n_tiles && (st = create_fold_state(s.get()))))
-    return st;
-  size_grids(s.get());
-  *out = s.release();
-  return SMCRT_OK;
+  if (const int st = plan_voxel_scene(labels, media, n_media, grid, dets, n_dets, read_knobs(), &plan)) return st;
+  return create_scene(std::move(plan), device,
+                      [](smcrt_scene* s) { return upload(s->d_labels, s->labels.data(), s->labels.size(), "label upload"); }, out);
 }
 
 int smcrt_mesh_scene_create(const double* verts, int32_t nv, const int32_t* tris, const uint8_t* tri_media, int32_t nt,
@@ -476,24 +475,16 @@ int smcrt_mesh_scene_create(const double* verts, int32_t nv, const int32_t* tris
   if (!out) return fail(SMCRT_ERR_INVALID_ARG, "out is NULL");
   *out = nullptr;
   ScenePlan plan;
-  int st = plan_mesh_scene(verts, nv, tris, tri_media, nt, media, n_media, ambient, grid, dets, n_dets, read_knobs(), &plan);
-  if (st) return st;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMCRT_ERR_NO_DEVICE, "no HIP device");
-  if (device < 0 || device >= ndev) return fail(SMCRT_ERR_INVALID_ARG, "device ordinal out of range");
-  std::unique_ptr<smcrt_scene, void (*)(smcrt_scene*)> s(new smcrt_scene(), smcrt_scene_destroy);
-  static_cast<ScenePlan&>(*s) = std::move(plan);
-  s->device = device;
-  if (hipSetDevice(device) != hipSuccess) return fail(SMCRT_ERR_HIP, "hipSetDevice failed");
-  if ((st = upload_plan(s.get())) ||
-      (st = upload(s->d_mesh_nodes, s->mesh_nodes.data(), s->mesh_nodes.size(), "mesh node upload")) ||
-      (st = upload(s->d_mesh_tris, s->mesh_tris.data(), s->mesh_tris.size(), "mesh triangle upload")) ||
-      (st = upload(s->d_mesh_faces, s->mesh_faces.data(), s->mesh_faces.size(), "mesh face upload")) ||
-      (s->n_tiles && (st = create_fold_state(s.get()))))
+  if (const int st = plan_mesh_scene(verts, nv, tris, tri_media, nt, media, n_media, ambient, grid, dets, n_dets,
+                                     read_knobs(), &plan))
     return st;
-  size_grids(s.get());
-  *out = s.release();
-  return SMCRT_OK;
+  return create_scene(std::move(plan), device, [](smcrt_scene* s) {
+    int st;
+    if ((st = upload(s->d_mesh_nodes, s->mesh_nodes.data(), s->mesh_nodes.size(), "mesh node upload")) ||
+        (st = upload(s->d_mesh_tris, s->mesh_tris.data(), s->mesh_tris.size(), "mesh triangle upload")))
+      return st;
+    return upload(s->d_mesh_faces, s->mesh_faces.data(), s->mesh_faces.size(), "mesh face upload");
+  }, out);
 }
 
 int smcrt_scene_det_bins(const smcrt_scene* s, int64_t* n) {
@@ -612,8 +603,6 @@ static hipError_t drain_folds(smcrt_scene* s) {
   return e;
 }
 
-static int transport_blocks(const smcrt_scene* s) { return std::max(s->grid_blocks, s->grid_blocks_x); }
-
 // Make sure the record pool holds `records` (grow only). Returns false if it cannot.
 static bool ensure_pool(smcrt_scene* s, uint64_t records) {
   // (the pool is counted in CHUNK_RECORDS units on both paths: a chunk is 64 buckets)
@@ -687,7 +676,7 @@ static int next_timing_events(smcrt_scene* s, Event** ev) {
 
 // One transport launch on `stream` (queue index qi) into record slot `sl` (binned): the
 // launch's cold parameters, the cleared queue head and deposit state, then the kernel.
-static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xsrc, bool lean, hipStream_t stream,
+static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, const LaunchChoice& c, hipStream_t stream,
                              int sl, int qi, Event** ev_out) {
   const bool binned = K.rec_pool != nullptr;
   if (binned && s->f_pending[sl]) HIPCHK(hipStreamWaitEvent(stream, s->ev_f[sl], 0));  // slot free
@@ -709,42 +698,20 @@ static int enqueue_transport(smcrt_scene* s, const KParams& K, KCold Ch, bool xs
   if (const int st = next_timing_events(s, ev_out)) return st;
   Event* ev = *ev_out;
   if (ev) HIPCHK(hipEventRecord(ev[0], stream));
-  const uint64_t waves_needed = (Ch.n_photons + 63) / 64;
-  const uint64_t blocks_needed = (waves_needed + 3) / 4;
-  const uint64_t ws_needed = (Ch.n_photons + kinst_ws_photon_lanes() - 1) / kinst_ws_photon_lanes();
-  const bool hist = (K.flags & SMCRT_FLAG_TRACK_PATHS) && s->path_on;  // (never lean: launch_lean)
-  const bool phas = (K.flags & SMCRT_FLAG_PHASOR) && s->phasor_on && !hist;  // (likewise; never with hist: smcrt_run)
-  // (the kernel sizes its start-point rows by the very count it reads from this KCold)
-  const bool scr = phas && Ch.n_screens > 0;
-  const int blocks = (int)std::min<uint64_t>(
-      (uint64_t)(lean ? s->grid_blocks_ws
-                      : hist ? s->grid_blocks_hist[xsrc ? 1 : 0]
-                             : scr ? s->grid_blocks_phas_scr[xsrc ? 1 : 0]
-                                   : phas ? s->grid_blocks_phas[xsrc ? 1 : 0] : (xsrc ? s->grid_blocks_x : s->grid_blocks)),
-      std::max<uint64_t>(1, lean ? ws_needed : blocks_needed));
+  // as many blocks as the photons need: waves of 64 in blocks of 4, or ws_kernel's photon lanes per block
+  const bool ws = c.family == KF_WS;
+  const uint64_t per_block = ws ? (uint64_t)kinst_ws_photon_lanes() : 256;
+  const int blocks = (int)std::min<uint64_t>((uint64_t)blocks_for(s, c),
+                                             std::max<uint64_t>(1, (Ch.n_photons + per_block - 1) / per_block));
+  if (ws) ++s->lean_launches;
+  // ws_kernel takes (K, nodes, prog, C); transport_kernel, voxel_kernel and mesh_kernel the detectors too
   const smcrt_sdf_node* a_nodes = K.nodes;
   const ProgOp* a_prog = K.prog;
-  if (s->voxel || s->mesh) {  // voxel_kernel (voxel.h), mesh_kernel (mesh.h): transport_kernel's arguments
-    const smcrt_detector* a_dets = K.dets;
-    const int64_t* a_off = K.det_off;
-    void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&a_dets, (void*)&a_off, (void*)&C};
-    HIPCHK(hipLaunchKernel(s->mesh ? mesh_kernel_ptr(s->grid_mode, xsrc) : voxel_kernel_ptr(s->grid_mode, xsrc),
-                           dim3(blocks), dim3(256), args,
-                           s->mesh ? mesh_lds(*s, dep_words(*s)) : voxel_lds(*s, dep_words(*s)), stream));
-  } else if (lean) {
-    ++s->lean_launches;
-    void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&C};
-    const bool xf = s->d_lscratch != nullptr;
-    const bool tk = (K.flags & SMCRT_FLAG_TEST_KERNEL) != 0;
-    HIPCHK(hipLaunchKernel(ws_kernel_ptr(s->lds_faces, s->grid_mode, xf, s->ws_slots, ws_invoxel_on(s->ws_invoxel, xf), tk),
-                           dim3(blocks), dim3(kinst_ws_threads()), args, lean_lds(*s), stream));
-  } else {
-    const smcrt_detector* a_dets = K.dets;
-    const int64_t* a_off = K.det_off;
-    void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&a_dets, (void*)&a_off, (void*)&C};
-    HIPCHK(hipLaunchKernel(transport_fn(s, xsrc, hist, phas), dim3(blocks), dim3(256), args,
-                           transport_lds(*s, dep_words(*s), xsrc, hist || phas, scr), stream));
-  }
+  const smcrt_detector* a_dets = K.dets;
+  const int64_t* a_off = K.det_off;
+  void* args_ws[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&C};
+  void* args[] = {(void*)&K, (void*)&a_nodes, (void*)&a_prog, (void*)&a_dets, (void*)&a_off, (void*)&C};
+  HIPCHK(hipLaunchKernel(kernel_ptr(c), dim3(blocks), dim3(kernel_threads(c)), ws ? args_ws : args, c.lds, stream));
   HIPCHK(hipGetLastError());
   if (ev) HIPCHK(hipEventRecord(ev[1], stream));
   return SMCRT_OK;
@@ -861,12 +828,12 @@ static int diag_report(hipStream_t stream, bool lean) {
 
 // One launch: the transport kernel on `stream`, then its fold on s->fstream.
 static int launch_one(smcrt_scene* s, const KParams& K, const KCold& Ch, bool xsrc, hipStream_t stream, int sl, int qi) {
-  const bool lean = launch_lean(s->lean_ok, xsrc, K.bucket_tiles, K.flags);
+  const LaunchChoice c = launch_choice(*s, s->lean_ok, xsrc, K.bucket_tiles, K.flags, s->path_on, s->phasor_on, s->screens.size());
   Event* ev = nullptr;
-  int st = enqueue_transport(s, K, Ch, xsrc, lean, stream, sl, qi, &ev);
+  int st = enqueue_transport(s, K, Ch, c, stream, sl, qi, &ev);
   if (!st) st = enqueue_fold(s, K, Ch.jmean, stream, sl, ev);
 #ifdef SMCRT_DIAG
-  if (!st) st = diag_report(stream, lean);
+  if (!st) st = diag_report(stream, c.family == KF_WS);
 #endif
   return st;
 }
@@ -881,7 +848,7 @@ struct OriginRun {
 // The parameters every batch of a launch shares (launch() sets the per-batch pool fields).
 static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_config* cfg,
                        const smcrt_device_tallies& dt, const SrcPlan& plan, hipStream_t stream, bool diag_done_ok,
-                       KParams& K, KCold& Ch) {
+                       const LaunchChoice& run, KParams& K, KCold& Ch) {
   const LaunchKnobs knobs = read_launch_knobs();
   K.nodes = s->d_nodes;
   K.prog = s->d_prog;
@@ -920,7 +887,7 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.invoxel_segs = s->d_queue + Q_INVOXEL;
   Ch.lane_scratch = nullptr;  // (per launch stream: enqueue_transport)
   Ch.watchdog = watchdog_word(s);
-  const bool hist = (cfg->flags & SMCRT_FLAG_TRACK_PATHS) && s->path_on;
+  const bool hist = run.hist, phas = run.phas, scr = run.scr;  // (the run's launch choice)
   Ch.hist_scratch = hist ? (double*)s->d_hist_scratch : nullptr;
   Ch.path_vertices = hist ? (double*)s->d_path_vertices : nullptr;
   Ch.path_headers = hist ? (smcrt_path*)s->d_path_headers : nullptr;
@@ -932,7 +899,6 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.hist_max_vertices = hist ? (uint32_t)s->path_cfg.max_vertices : 0;
   // the phasor tally: the wavenumber of photons that sample no wavelength of their own is the
   // fixed one, or 2 pi / the constant spectrum's value (NULL spectrum: 500.0, smcrt.h)
-  const bool phas = (cfg->flags & SMCRT_FLAG_PHASOR) && s->phasor_on;
   Ch.phasor = phas ? (double*)s->d_phasor : nullptr;
   Ch.phasor_fixed = phas && s->phasor_cfg.fixed_k ? 1u : 0u;
   Ch.phasor_k = !phas ? 0.0
@@ -940,7 +906,6 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
                                         : 6.283185307179586 / (src->spectrum ? src->spectrum->wavelength : 500.0);
   // field screens and the optical-path option: a phasor launch only (a voxel or a mesh scene
   // has neither: smcrt_scene_set_phasor and smcrt_scene_set_screens refuse them)
-  const bool scr = phas && !s->screens.empty() && s->d_screens && s->d_screen_field;
   Ch.screens = scr ? (const ScreenDev*)s->d_screens : nullptr;
   Ch.screen_field = scr ? (double*)s->d_screen_field : nullptr;
   Ch.n_screens = scr ? (uint32_t)s->screens.size() : 0u;
@@ -979,7 +944,7 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   K.rec_pool = nullptr; K.n_chunks = 0; K.hist_tiles = 0; K.bucket_tiles = 0; K.n_buckets = 0;
   K.claim_delay = knobs.claim_delay;
   K.lean_debug = s->lean_debug | (knobs.drop_event ? 4u : 0u);
-  K.ws_invoxel = ws_invoxel_on(s->ws_invoxel, s->d_lscratch != nullptr) ? 1u : 0u;
+  K.ws_invoxel = ws_invoxel_on(s->ws_invoxel, plan_xf(*s)) ? 1u : 0u;  // (read by ws_kernel only)
   lean_margins(K.lean_debug, s->grid, K.lean_lo, K.lean_hi);
   return SMCRT_OK;
 }
@@ -1033,7 +998,9 @@ static int launch(smcrt_scene* s, const smcrt_source* src, const smcrt_run_confi
   }
   KParams K;
   KCold Ch;
-  if (const int st = fill_params(s, src, cfg, dt, plan, stream, !orun, K, Ch)) return st;
+  // (hist, phas and scr are those of every batch: a batch that runs ws_kernel has none of the three)
+  const LaunchChoice run = launch_choice(*s, false, xsrc, 0, cfg->flags, s->path_on, s->phasor_on, s->screens.size());
+  if (const int st = fill_params(s, src, cfg, dt, plan, stream, !orun, run, K, Ch)) return st;
   const bool binned = launch_binned(*s, dt.jmean != nullptr, cfg->flags);
   const bool overlap = (cfg->flags & SMCRT_FLAG_OVERLAP) != 0;
   if (overlap) {  // the internal streams start after the caller's earlier work
@@ -1179,18 +1146,11 @@ static int run_sync(smcrt_scene* s, const smcrt_source* src, const smcrt_run_con
       if (gd[t]) gd[t][i] += h[i];
     }
   }
-  std::vector<double> small((size_t)s->det_total + 25);
-  HIPCHK(hipMemcpy(small.data(), s->d_small, sizeof(double) * small.size(), hipMemcpyDeviceToHost));
-  if (io->det_bins)
-    for (int64_t i = 0; i < s->det_total; ++i) io->det_bins[i] += small[i];
-  if (io->nscatt) *io->nscatt += small[s->det_total];
-  if (io->moments)
-    for (int i = 0; i < 24; ++i) io->moments[i] += small[s->det_total + 1 + i];
-  if (io->counters) {
-    unsigned long long c[SMCRT_NCOUNTERS];
-    HIPCHK(hipMemcpy(c, s->d_counters, sizeof(c), hipMemcpyDeviceToHost));
-    for (int i = 0; i < SMCRT_NCOUNTERS; ++i) io->counters[i] += c[i];
-  }
+  const double* small = s->d_small;  // det bins | nscatt | moments(24)
+  if (io->det_bins) HIPCHK(read_add(s, small, (size_t)s->det_total, io->det_bins));
+  if (io->nscatt) HIPCHK(read_add(s, small + s->det_total, 1, io->nscatt));
+  if (io->moments) HIPCHK(read_add(s, small + s->det_total + 1, 24, io->moments));
+  if (io->counters) HIPCHK(read_add(s, (const unsigned long long*)s->d_counters, SMCRT_NCOUNTERS, io->counters));
   if (rec)
     HIPCHK(hipMemcpy(io->records, s->d_records, sizeof(smcrt_photon_record) * cfg->n_photons, hipMemcpyDeviceToHost));
   return SMCRT_OK;
@@ -1252,12 +1212,8 @@ int smcrt_run_origins(smcrt_scene* s, const smcrt_source* src, const double* ori
     if (e == hipSuccess) e = hipMemset(d_tot, 0, sizeof(double) * nt);
     if (e != hipSuccess) st = fail(SMCRT_ERR_HIP, std::string("origin upload: ") + hipGetErrorString(e));
     if (!st) st = run_sync(s, &p, &c, io, &orun);
-    if (!st && det_totals && s->n_dets) {
-      std::vector<double> h(nt);
-      e = hipMemcpy(h.data(), d_tot, sizeof(double) * nt, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) st = fail(SMCRT_ERR_HIP, std::string("totals: ") + hipGetErrorString(e));
-      else for (size_t i = 0; i < nt; ++i) det_totals[i] += h[i];
-    }
+    if (!st && det_totals && s->n_dets && (e = read_add(s, (const double*)d_tot, nt, det_totals)) != hipSuccess)
+      st = fail(SMCRT_ERR_HIP, std::string("totals: ") + hipGetErrorString(e));
   }
   return st;
 }
@@ -1445,15 +1401,10 @@ int smcrt_scene_set_path_tracking(smcrt_scene* s, const smcrt_path_config* cfg) 
   HIPCHK(hipStreamSynchronize(s->stream));  // (no launch of this scene may still use the buffers)
   release_paths(s);
   if (!cfg) return SMCRT_OK;
-  int cus = s->n_cus;
-  for (int x = 0; x < 2; ++x) {  // the HIST instantiations' persistent grids
-    int per_cu = 0;
-    const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, transport_fn(s, x == 1, true), 256,
-                                                                       transport_lds(*s, dep_words(*s), x == 1, true));
-    if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-    s->grid_blocks_hist[x] = cus * per_cu;
-  }
-  const uint64_t lanes = (uint64_t)std::max(s->grid_blocks_hist[0], s->grid_blocks_hist[1]) * 256ull;
+  int hist_blocks = 0;  // the larger of the HIST instantiations' persistent grids (plain, XSRC)
+  for (int x = 0; x < 2; ++x)
+    hist_blocks = std::max(hist_blocks, blocks_for(s, launch_choice(*s, false, x == 1, 0, SMCRT_FLAG_TRACK_PATHS, true, false, 0)));
+  const uint64_t lanes = (uint64_t)hist_blocks * 256ull;
   const uint64_t mv = (uint64_t)cfg->max_vertices, mp = (uint64_t)cfg->max_paths;
   if (mp > (1ull << 40) / mv) return fail(SMCRT_ERR_OOM, "path tracking: the arena does not fit");
   int st;
@@ -1535,19 +1486,6 @@ int smcrt_scene_read_paths(smcrt_scene* s, smcrt_path* paths, double* vertices) 
 }
 
 // ---- the phasor tally (phasor.h) ----------------------------------------------------
-// The persistent grids of the PHAS instantiations (plain, XSRC), without and with the screens'
-// rows of start-point LDS.
-static void phas_grids(smcrt_scene* s) {
-  for (int scr = 0; scr < 2; ++scr)
-    for (int x = 0; x < 2; ++x) {
-      int per_cu = 0;
-      const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &per_cu, transport_fn(s, x == 1, false, true), 256, transport_lds(*s, dep_words(*s), x == 1, true, scr == 1));
-      if (oe != hipSuccess || per_cu < 1) per_cu = 1;
-      (scr ? s->grid_blocks_phas_scr : s->grid_blocks_phas)[x] = s->n_cus * per_cu;
-    }
-}
-
 int smcrt_scene_set_phasor(smcrt_scene* s, const smcrt_phasor_config* cfg) {
   g_last_error.clear();
   if (cfg && cfg->fixed_k && !(cfg->wavenumber >= 0.0 && cfg->wavenumber <= 0x1.fffffffffffffp+1023))
@@ -1562,7 +1500,8 @@ int smcrt_scene_set_phasor(smcrt_scene* s, const smcrt_phasor_config* cfg) {
   s->phasor_on = false;
   s->d_phasor.reset();
   if (!cfg) return SMCRT_OK;
-  phas_grids(s);
+  for (int scr = 0; scr < 2; ++scr)  // the PHAS instantiations' grids (plain, XSRC), without and with the screens' LDS row
+    for (int x = 0; x < 2; ++x) (void)blocks_for(s, launch_choice(*s, false, x == 1, 0, SMCRT_FLAG_PHASOR, false, true, scr));
   const size_t n2 = 2 * (size_t)s->grid.nx * (size_t)s->grid.ny * (size_t)s->grid.nz;
   if (const int st = dalloc(s->d_phasor, n2)) {
     (void)hipGetLastError();
@@ -1581,12 +1520,7 @@ int smcrt_scene_read_phasor(smcrt_scene* s, double* out) {
   if (const int vst = smcrt::scene_needs_sdf(s, "the phasor tally")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   if (!s->phasor_on) return fail(SMCRT_ERR_INVALID_ARG, "the phasor tally is not configured on this scene");
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  const size_t n2 = 2 * (size_t)s->grid.nx * (size_t)s->grid.ny * (size_t)s->grid.nz;
-  std::vector<double> h(n2);
-  HIPCHK(hipMemcpy(h.data(), s->d_phasor, n2 * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < n2; ++i) out[i] += h[i];
+  HIPCHK(read_add(s, (const double*)s->d_phasor, 2 * (size_t)s->grid.nx * (size_t)s->grid.ny * (size_t)s->grid.nz, out));
   return SMCRT_OK;
 }
 
@@ -1596,11 +1530,7 @@ int smcrt_scene_reset_phasor(smcrt_scene* s) {
   if (const int vst = smcrt::scene_needs_sdf(s, "the phasor tally")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   if (!s->phasor_on) return fail(SMCRT_ERR_INVALID_ARG, "the phasor tally is not configured on this scene");
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  const size_t n2 = 2 * (size_t)s->grid.nx * (size_t)s->grid.ny * (size_t)s->grid.nz;
-  HIPCHK(hipMemset(s->d_phasor, 0, n2 * sizeof(double)));
-  return SMCRT_OK;
+  return zero_tally(s, s->d_phasor, 2 * (size_t)s->grid.nx * (size_t)s->grid.ny * (size_t)s->grid.nz);
 }
 
 // ---- field screens (screen.h, phasor.h screen_hits) -------------------------------------
@@ -1649,11 +1579,7 @@ int smcrt_scene_read_screens(smcrt_scene* s, double* out) {
   if (const int vst = smcrt::scene_needs_sdf(s, "field screens")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   if (s->screens.empty()) return fail(SMCRT_ERR_INVALID_ARG, "no screens are configured on this scene");
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  std::vector<double> h((size_t)s->screen_doubles);
-  HIPCHK(hipMemcpy(h.data(), s->d_screen_field, h.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (size_t i = 0; i < h.size(); ++i) out[i] += h[i];
+  HIPCHK(read_add(s, (const double*)s->d_screen_field, (size_t)s->screen_doubles, out));
   return SMCRT_OK;
 }
 
@@ -1663,10 +1589,7 @@ int smcrt_scene_reset_screens(smcrt_scene* s) {
   if (const int vst = smcrt::scene_needs_sdf(s, "field screens")) return vst;
   std::lock_guard<std::mutex> g(s->mu);
   if (s->screens.empty()) return fail(SMCRT_ERR_INVALID_ARG, "no screens are configured on this scene");
-  HIPCHK(hipSetDevice(s->device));
-  HIPCHK(hipStreamSynchronize(s->stream));
-  HIPCHK(hipMemset(s->d_screen_field, 0, (size_t)s->screen_doubles * sizeof(double)));
-  return SMCRT_OK;
+  return zero_tally(s, s->d_screen_field, (size_t)s->screen_doubles);
 }
 
 int smcrt_screen_hit(const smcrt_screen* screen, const double start[3], const double dir[3], double sep, double* t,

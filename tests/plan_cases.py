@@ -259,6 +259,70 @@ def kernel_of(p, xsrc, flags=abi.FLAG_PATHLENGTH, dets=()):
     return ("transport_kernel", lds, f["grid_mode"], int(xsrc), f["coop"])
 
 
+CTAB_BYTES = 21 * 64 * 8  # transport.h CTAB_DOUBLES doubles: the cooperative EVAL's primitive table
+# (name, flags, lean_ok, paths_on, phasor_on, n_screens): the run states whose choice
+# tests/test_sceneplan.py compares with the probe's
+RUN_STATES = (
+    ("plain", abi.FLAG_PATHLENGTH, 1, 0, 0, 0),
+    ("survival-bias", abi.FLAG_PATHLENGTH | abi.FLAG_SURVIVAL_BIAS, 1, 0, 0, 0),
+    ("test-kernel", abi.FLAG_PATHLENGTH | abi.FLAG_TEST_KERNEL, 1, 0, 0, 0),
+    ("paths-on", abi.FLAG_PATHLENGTH | abi.FLAG_TRACK_PATHS, 1, 1, 0, 0),
+    ("paths-unset", abi.FLAG_PATHLENGTH | abi.FLAG_TRACK_PATHS, 1, 0, 0, 0),
+    ("phasor-on", abi.FLAG_PATHLENGTH | abi.FLAG_PHASOR, 1, 0, 1, 0),
+    ("phasor-unset", abi.FLAG_PATHLENGTH | abi.FLAG_PHASOR, 1, 0, 0, 0),
+    ("phasor-screens", abi.FLAG_PATHLENGTH | abi.FLAG_PHASOR, 1, 0, 1, 2),
+    ("phasor-unset-screens", abi.FLAG_PATHLENGTH | abi.FLAG_PHASOR, 1, 0, 0, 2),
+    ("no-lean", abi.FLAG_PATHLENGTH, 0, 0, 0, 0),
+)
+
+
+def run_state_of(flags, paths_on, phasor_on, n_screens):
+    """(hist, phas, scr) of a launch of transport_kernel: the path recorder when
+    the run asks for paths and tracking is configured, else the phasor tally when the run asks for
+    it and it is configured (never both), and the screens' LDS row when that tally has screens."""
+    hist = bool(flags & abi.FLAG_TRACK_PATHS) and bool(paths_on)
+    phas = bool(flags & abi.FLAG_PHASOR) and bool(phasor_on) and not hist
+    return hist, phas, phas and n_screens > 0
+
+
+def dep_bytes_of(p):
+    """A block's deposit state in LDS (deposit.h): a 64-bit bucket word per tile, or a tile
+    histogram per wave."""
+    return 4 * (2 * p["n_tiles"] if p["bucketed"] else 4 * p["hist_tiles"])
+
+
+def choice_of(p, xsrc, flags=abi.FLAG_PATHLENGTH, dets=(), lean_ok=True, paths_on=False, phasor_on=False, n_screens=0,
+              kind="sdf", env=None):
+    """The whole launch choice for a probed plan, in the keys of planprobe.choices: `kernel_of`,
+    then hist / phas / scr, ws_kernel's TK and in-voxel coordinates, the dynamic LDS bytes, and
+    `grid`: launches with equal values share a persistent grid. Written from DESIGN.md §4 and the
+    launch sites smcrt.hip had before sceneplan.h launch_choice, not from that function."""
+    c = dict.fromkeys(("xsrc", "lds_faces", "coop", "hist", "phas", "xf", "slots", "iv", "tk", "scr"), 0)
+    c.update(gm=p["grid_mode"], block="256")
+    if kind in ("voxel", "mesh"):  # voxel_kernel<gm, xsrc>, mesh_kernel<gm, xsrc>: media + faces, then the deposit words
+        c.update(family=kind + "_kernel", xsrc=int(xsrc), lds=p["face_bytes"] + dep_bytes_of(p))
+        c["grid"] = (c["family"], c["xsrc"])
+        return c
+    k = kernel_of(p, xsrc, flags, dets)
+    tracked = flags & (abi.FLAG_TRACK_PATHS | abi.FLAG_PHASOR)  # ws_kernel has neither
+    if k[0] == "ws_kernel" and lean_ok and not tracked:
+        knob = (env or {}).get("SMCRT_WS_INVOXEL")  # on by default in the plain instantiation only
+        iv = int(not k[3]) if knob is None else int(knob != "0")
+        c.update(family="ws_kernel", lds_faces=k[1], xf=k[3], slots=k[4], iv=iv, tk=int(bool(flags & abi.FLAG_TEST_KERNEL)),
+                 block="ws", lds=(p["face_bytes"] if p["lds_faces"] else 0) + 8 * p["n_tiles"])
+        c["grid"] = ("ws_kernel",)  # (TK or not: same block, LDS and register cap)
+        return c
+    f = plan_fields(p, dets)
+    hist, phas, scr = run_state_of(flags, paths_on, phasor_on, n_screens)
+    faces = bool(f["lds_faces"]) and not (xsrc and f["coop"]) and not hist and not phas
+    rows = 4 if scr else 3 if len(dets) else 0  # start points: 256 doubles a row
+    c.update(family="transport_kernel", xsrc=int(xsrc), lds_faces=int(faces), coop=f["coop"], hist=int(hist), phas=int(phas),
+             scr=int(scr), lds=(p["face_bytes"] if faces else 0) + rows * 256 * 8 + dep_bytes_of(p) +
+             (CTAB_BYTES if p["ctab"] and f["coop"] else 0))
+    c["grid"] = ("transport_kernel", c["xsrc"], c["hist"], c["phas"], c["scr"])
+    return c
+
+
 def check_table():
     """The table covers what it claims: each of the 24 + 21 instantiations exactly once in the
     matrix, the deposit regimes at their five boundary sizes, six axis-bound and eight tiny

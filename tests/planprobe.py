@@ -68,6 +68,30 @@ def plan(sc, g, dets=(), env=None, nodes=None, top=None):
     return out
 
 
+def choices(sc, g, states, dets=(), env=None, kind="sdf"):
+    """The launch choices (sceneplan.h launch_choice) of the plan of `sc` on `g`, one dict per run
+    state (xsrc, flags, lean_ok, paths_on, phasor_on, n_screens): `family`, the template
+    coordinates, `block` ("ws" or "256"), `lds` and `grid_key`. `kind` "voxel" / "mesh" marks the
+    plan as such after planning (see the probe's header)."""
+    with tempfile.NamedTemporaryFile(suffix=".scene") as f:
+        f.write(_blob(sc, g, dets))
+        f.flush()
+        e = {k: v for k, v in os.environ.items() if not k.startswith("SMCRT_")}
+        e.update(env or {})
+        args = [str(int(v)) for st in states for v in st]
+        lines = subprocess.run([build(), "choice", f.name, kind, *args], env=e, check=True, capture_output=True,
+                               text=True).stdout.splitlines()
+    assert lines[0] == "status=0", lines[:2]
+    out = []
+    for line in lines[2:]:
+        k, v = line.split("=", 1)
+        if k == "family":
+            out.append({})
+        out[-1][k] = v if k in ("family", "block") else int(v)
+    assert len(out) == len(states)
+    return out
+
+
 def cull(sc, g, env=None):
     """The culling grid (cull.h CullHost) of the plan of `sc` on `g`, as the kernels read it: a
     dict with `enabled`, `n` (cells per axis), `lo`, `cell`, `off` (ncells + 1), `list` (entries

@@ -9,6 +9,13 @@
 //                               elb, lb | uint32 off[] | uint32 list[] | float elb[] | double lb[] |
 //                               int32 always[]
 //   sceneplan_probe slots LEAN_OR_FAR CAP_BYTES TOTAL_MEM
+//   sceneplan_probe choice FILE KIND (XSRC FLAGS LEAN_OK PATHS_ON PHASOR_ON N_SCREENS)...
+//                               the launch choice (sceneplan.h launch_choice) of the plan of FILE for each
+//                               run state, one block of lines from family= to grid_key= each; a launch that may deposit into buckets has the plan's tiles as its
+//                               bucket_tiles (launch_binned, as smcrt.hip's launch() sets them). KIND sdf
+//                               probes the plan as it is; voxel and mesh mark it as a voxel or a mesh plan
+//                               after planning (the choice for those reads only p.voxel, p.mesh, grid_mode,
+//                               face_bytes and the deposit words, so they need no file format of their own).
 // The SMCRT_* knobs come from the environment, through the readers the library uses.
 #include <cstdio>
 #include <cstdlib>
@@ -47,7 +54,21 @@ static int dump_cull(const CullHost& H, const char* path) {
   return std::fclose(f) == 0 && ok ? 0 : 2;
 }
 
-static int plan(const char* path, const char* cull_out = nullptr) {
+static void choice(const ScenePlan& p, char** a) {
+  const bool xsrc = std::atoi(a[0]) != 0;
+  const uint32_t flags = (uint32_t)std::strtoul(a[1], nullptr, 0);
+  const uint32_t bucket_tiles = launch_binned(p, true, flags) && p.bucketed ? p.n_tiles : 0;
+  const LaunchChoice c = launch_choice(p, std::atoi(a[2]) != 0, xsrc, bucket_tiles, flags, std::atoi(a[3]) != 0,
+                                       std::atoi(a[4]) != 0, (size_t)std::atoi(a[5]));
+  static const char* const family[] = {"transport_kernel", "ws_kernel", "voxel_kernel", "mesh_kernel"};
+  std::printf("family=%s\ngm=%d\nxsrc=%d\nlds_faces=%d\ncoop=%d\nhist=%d\nphas=%d\nxf=%d\nslots=%d\niv=%d\ntk=%d\nscr=%d\n",
+              family[c.family], c.gm, (int)c.xsrc, (int)c.lds_faces, (int)c.coop, (int)c.hist, (int)c.phas, (int)c.xf,
+              c.slots, (int)c.iv, (int)c.tk, (int)c.scr);
+  // (the block-size class: kernel_ptrs.h kernel_threads gives ws_kernel its own block, every other family 256)
+  std::printf("block=%s\nlds=%zu\ngrid_key=%d\n", c.family == KF_WS ? "ws" : "256", c.lds, c.grid_key());
+}
+
+static int plan(const char* path, const char* cull_out = nullptr, char** choice_args = nullptr, int n_choices = 0) {
   std::FILE* f = std::fopen(path, "rb");
   int32_t hdr[3];
   if (!f || std::fread(hdr, sizeof(int32_t), 3, f) != 3 || hdr[0] < 0 || hdr[1] < 0 || hdr[2] < 0) return 2;
@@ -64,6 +85,13 @@ static int plan(const char* path, const char* cull_out = nullptr) {
   std::printf("status=%d\nerror=%s\n", st, g_last_error.c_str());
   if (st) return 0;
   if (cull_out) return dump_cull(p.cull, cull_out);
+  if (choice_args) {
+    const std::string kind = choice_args[0];
+    p.voxel = kind == "voxel";
+    p.mesh = kind == "mesh";
+    for (int i = 0; i < n_choices; ++i) choice(p, choice_args + 1 + 6 * i);
+    return 0;
+  }
   std::printf("det_total=%lld\nh_det_off=", (long long)p.det_total);
   for (int64_t o : p.h_det_off) std::printf("%lld,", (long long)o);
   std::printf("\nn_prog=%d\nprog_size=%zu\nnested=%d\ncoop_lanes=%d\nctab=%d\ncull=%d\n", p.n_prog, p.prog.size(),
@@ -82,11 +110,13 @@ int main(int argc, char** argv) {
   const std::string mode = argc > 1 ? argv[1] : "";
   if (mode == "plan" && argc == 3) return plan(argv[2]);
   if (mode == "cull" && argc == 4) return plan(argv[2], argv[3]);
+  if (mode == "choice" && argc >= 10 && (argc - 4) % 6 == 0) return plan(argv[2], nullptr, argv + 3, (argc - 4) / 6);
   if (mode == "slots" && argc == 5) {
     std::printf("slots=%d\n", slot_depth(read_pool_knobs(), std::atoi(argv[2]) != 0, std::strtoull(argv[3], nullptr, 10),
                                          std::strtoull(argv[4], nullptr, 10)));
     return 0;
   }
-  std::fprintf(stderr, "usage: sceneplan_probe plan FILE | cull FILE OUT | slots LEAN_OR_FAR CAP_BYTES TOTAL_MEM\n");
+  std::fprintf(stderr, "usage: sceneplan_probe plan FILE | cull FILE OUT | slots LEAN_OR_FAR CAP_BYTES TOTAL_MEM | "
+                       "choice FILE KIND (XSRC FLAGS LEAN_OK PATHS_ON PHASOR_ON N_SCREENS)...\n");
   return 2;
 }

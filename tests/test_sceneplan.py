@@ -143,6 +143,59 @@ def test_plan_table(case):
     assert p["n_tiles"] == (plan_cases.tiles_of(case.grid) if plan_cases.tiles_of(case.grid) <= 4096 else 0)
 
 
+def _check_choices(sc, g, p, dets=(), env=None, kind="sdf"):
+    """The probe's launch choice against plan_cases.choice_of for both values of xsrc and every
+    run state of plan_cases.RUN_STATES, and the grid keys: equal exactly where the restatement
+    says two launches share a grid."""
+    # (the library's lean_ok is the plan's lean_candidate, unless the lane-scratch allocation failed: "no-lean")
+    states = [(x, st[1], st[2] and p["lean_candidate"]) + st[3:] for x in (0, 1) for st in plan_cases.RUN_STATES]
+    got = planprobe.choices(sc, g, states, dets, env, kind)
+    want = [plan_cases.choice_of(p, x, fl, dets, lean_ok, paths, phasor, n_scr, kind, env)
+            for x, fl, lean_ok, paths, phasor, n_scr in states]
+    for st, c, w in zip(states, got, want):
+        assert {k: v for k, v in c.items() if k != "grid_key"} == {k: v for k, v in w.items() if k != "grid"}, st
+    for i in range(len(states)):
+        for j in range(i):
+            assert (got[i]["grid_key"] == got[j]["grid_key"]) == (want[i]["grid"] == want[j]["grid"]), (states[i], states[j])
+    return got
+
+
+@pytest.mark.parametrize("case", plan_cases.CASES, ids=[c.id for c in plan_cases.CASES])
+def test_launch_choice_table(case):
+    """sceneplan.h launch_choice, which the occupancy query and the launch both read, against the
+    independent restatement of tests/plan_cases.py for every case of the table."""
+    sc, g = case.scene(), case.scene_grid()
+    p = planprobe.plan(sc, g, env=case.env)
+    got = _check_choices(sc, g, p, env=case.env)
+    plain = got[[case.xsrc == x and st[0] == "plain" for x in (0, 1) for st in plan_cases.RUN_STATES].index(True)]
+    assert (plain["family"] == "ws_kernel") == case.lean
+
+
+@pytest.mark.parametrize("kind", ["voxel", "mesh"])
+@pytest.mark.parametrize("gm", [2, 1, 0])
+def test_launch_choice_voxel_and_mesh(kind, gm):
+    case = plan_cases.BY_ID[f"ws-F1-G{gm}-xf0-s3"]
+    sc, g = case.scene(), case.scene_grid()
+    p = planprobe.plan(sc, g)
+    assert p["grid_mode"] == gm
+    got = _check_choices(sc, g, p, kind=kind)
+    assert {c["family"] for c in got} == {kind + "_kernel"} and {c["grid_key"] for c in got} == {0, 1}
+
+
+def test_launch_choice_with_detectors_and_the_invoxel_knob():
+    """Detectors make a scene XF and give transport_kernel its start-point rows; SMCRT_WS_INVOXEL
+    overrides the in-voxel coordinate either way."""
+    sc, g, dets = skin()
+    for env in ({}, {"SMCRT_LEAN": "1"}, {"SMCRT_LEAN": "1", "SMCRT_WS_INVOXEL": "1"}):
+        got = _check_choices(sc, g, planprobe.plan(sc, g, dets, env=env), dets, env)
+        assert (got[0]["family"], got[0]["xf"], got[0]["iv"]) == (("ws_kernel", 1, int("SMCRT_WS_INVOXEL" in env))
+                                                                  if env else ("transport_kernel", 0, 0))
+    sc, g = sphere()
+    for env, iv in (({}, 1), ({"SMCRT_WS_INVOXEL": "0"}, 0)):
+        got = _check_choices(sc, g, planprobe.plan(sc, g, env=env), env=env)
+        assert (got[0]["family"], got[0]["xf"], got[0]["iv"]) == ("ws_kernel", 0, iv)
+
+
 def test_design_coverage_table_cites_the_cases():
     """DESIGN.md §3.3b names, for each instantiation and deposit regime, the test id that runs
     it: every matrix and deposit case of the table is cited there by its id."""
