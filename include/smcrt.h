@@ -246,8 +246,12 @@ enum {
                                           smcrt_scene_fence (implies SMCRT_FLAG_ASYNC_FOLD) */
   SMCRT_FLAG_TRACK_PATHS = 1u << 8,    /* smcrt_run only: record photon paths into the arena configured with
                                           smcrt_scene_set_path_tracking (see "photon paths" below) */
-  SMCRT_FLAG_PHASOR = 1u << 9          /* smcrt_run only: accumulate the complex phasor grid configured with
+  SMCRT_FLAG_PHASOR = 1u << 9,         /* smcrt_run only: accumulate the complex phasor grid configured with
                                           smcrt_scene_set_phasor (see "phasor tally" below) */
+  SMCRT_FLAG_PARTIAL_PATHS = 1u << 10  /* smcrt_run only, voxel and mesh scenes only, with SMCRT_FLAG_PATHLENGTH:
+                                          record the length of recorded photons in every medium into the arena
+                                          configured with smcrt_scene_set_partial_paths (see "partial path
+                                          lengths" below) */
 };
 
 typedef struct smcrt_run_config {
@@ -548,6 +552,81 @@ int smcrt_scene_path_counts(smcrt_scene* scene, int64_t* n_paths, int64_t* n_ver
 /* The n_paths records sorted by (photon, hit), and their n_vertices stored vertices (4 doubles
  * each: x, y, z, step) in the same order; paths[i].offset is path i's first vertex. */
 int smcrt_scene_read_paths(smcrt_scene* scene, smcrt_path* paths, double* vertices /* 4 per stored vertex */);
+
+/* ---- partial path lengths (voxel and mesh scenes; no counterpart in the reference) -------------
+ * The length a recorded photon travelled in every medium: what a time of flight (sum of
+ * n_m * len_m / c), the detector signal under another absorption (w * exp(-sum of dmua_m * len_m),
+ * "white" Monte Carlo) and the sensitivity of a measurement to a layer are computed from
+ * (rsmcrt_amd/partialpaths.py). A run with SMCRT_FLAG_PARTIAL_PATHS keeps, for every photon,
+ * len[m], one fp64 per medium of the scene, by this rule, operation by operation:
+ *  - len[0 .. n_media) = 0 at the photon's emission (every emission of the photon, so at the
+ *    accepted one);
+ *  - the walk goes piece by piece, one voxel crossing each, in the order of the photon's path. For
+ *    every piece whose crossing reports a deposit (every piece but one that ends in an error stop
+ *    of the crossing: what SMCRT_CTR_DEPOSITS counts in a path-length run) len[layer - 1] = len[layer
+ *    - 1] + dc, where `layer` is the photon's medium + 1 while it walks the piece (voxel scenes:
+ *    the medium of the voxel being left; mesh scenes: the medium of the leg) and dc is the piece's
+ *    length in fp64, before it is rounded to the float that the fluence tally adds;
+ *  - nothing else is added.
+ * So a photon's lengths are those the fluence tally sees: the sum of len[m] over all photons is
+ * the sum of jmean over the voxels of medium m up to the float rounding of each piece, and a
+ * photon's lengths do not depend on scheduling, shard or launch split. The 1e-8 step that a
+ * photon takes across each voxel wall (update_pos, inttau2.f90:524-584) is in no piece: a straight
+ * path through k walls is short by k * 1e-8 / |dir_axis| of each crossed axis. A leg of a mesh
+ * scene outside the grid deposits nothing and adds nothing.
+ * Two triggers file a record (a smcrt_ppath header and n_media doubles):
+ *  - every hit of every detector files the lengths up to the end of the leg that scored, where
+ *    the photon stands when detectors are evaluated (header: the leg that hit, as record_hit
+ *    receives it; start, dir and point_sep let a caller take off what lies behind the detector's
+ *    plane); the photon goes on, a later hit files longer lengths;
+ *  - photons with global index in [range_first, range_first + range_count) file their final
+ *    lengths when they finish (detector = -1, the final status and weight), faulted photons
+ *    included (status 3).
+ * Records go into an arena of max_records slots on the device; a record that finds no slot is
+ * counted as dropped. The ordinary tallies of a tracking run are those of the same run without
+ * the flag.
+ * The accumulator lives in the kernels' LDS, 2 KiB per medium and 256-thread block, so tracking
+ * is limited to scenes of at most SMCRT_PPATH_MAX_MEDIA media: 32 KiB, which with the kernels'
+ * 18 KiB of counters, at most 40 KiB of media and faces and at most 8 KiB of deposit words is 98
+ * KiB of the 160 KiB a block may hold, for every grid a scene can be created with. A tracking
+ * launch holds fewer blocks per CU than an untracked one once its LDS no longer fits four times
+ * (on a small grid: above 10 media). */
+#define SMCRT_PPATH_MAX_MEDIA 16
+
+typedef struct smcrt_ppath_config {
+  uint64_t range_first, range_count; /* the range trigger; range_count 0: none */
+  int64_t max_records;               /* >= 1 arena slots */
+  int64_t reserved;                  /* 0 */
+} smcrt_ppath_config;
+
+typedef struct smcrt_ppath {
+  uint64_t photon;   /* global photon index */
+  int32_t detector;  /* index of the detector that was hit, or -1 (range trigger) */
+  uint32_t hit;      /* ordinal of this record among the photon's records (0, 1, ...) */
+  uint32_t status;   /* range trigger: smcrt_photon_record.status; detector trigger: 0 */
+  int32_t layer;     /* detector trigger: the hit leg (record_hit's arguments) ... */
+  uint32_t nscatt;   /* scatters so far */
+  int32_t reserved;
+  double start[3], dir[3], point_sep, weight; /* ... range trigger: final pos, dir, 0, weight */
+} smcrt_ppath;
+
+/* Configure (or, with cfg NULL, turn off and free) partial path lengths on a voxel or a mesh
+ * scene: allocates the arena. Validated before any device call: max_records >= 1, reserved == 0,
+ * range_first + range_count does not overflow, the arena fits (SMCRT_ERR_OOM otherwise); a scene
+ * of more than SMCRT_PPATH_MAX_MEDIA media answers SMCRT_ERR_UNSUPPORTED naming the cap, an SDF
+ * scene SMCRT_ERR_UNSUPPORTED naming SDF scenes (as do the two functions below).
+ * SMCRT_FLAG_PARTIAL_PATHS is accepted by smcrt_run on a configured voxel or mesh scene, together
+ * with SMCRT_FLAG_PATHLENGTH: without either it is SMCRT_ERR_INVALID_ARG, as it is in
+ * smcrt_run_device; on an SDF scene and in smcrt_multi_* it is SMCRT_ERR_UNSUPPORTED. Without the
+ * flag a configured scene runs exactly as it does without the configuration. */
+int smcrt_scene_set_partial_paths(smcrt_scene* scene, const smcrt_ppath_config* cfg);
+/* Records in the arena since the last tracking smcrt_run started (each such run clears it; the
+ * arena stays readable until the next one) and records dropped for want of a slot. Either
+ * output may be NULL. */
+int smcrt_scene_partial_path_counts(smcrt_scene* scene, int64_t* n_records, int64_t* n_dropped);
+/* The n_records headers sorted by (photon, hit), and their lengths in the same order: n_records
+ * x n_media doubles, record i's medium m at lengths[i * n_media + m]. */
+int smcrt_scene_read_partial_paths(smcrt_scene* scene, smcrt_ppath* headers, double* lengths);
 
 /* ---- phasor tally (the reference's phase tracking: photon%phase, photon%fact, iarray phasor) --
  * The reference gives every packet a phase and fact = 2 pi / wavelength, adds each voxel piece

@@ -65,6 +65,8 @@ FLAG_ASYNC_FOLD = 1 << 6
 FLAG_OVERLAP = 1 << 7
 FLAG_TRACK_PATHS = 1 << 8  # smcrt_run only: record photon paths (Engine.set_path_tracking)
 FLAG_PHASOR = 1 << 9  # smcrt_run only: accumulate the complex phasor grid (Engine.set_phasor)
+# smcrt_run only, voxel and mesh scenes, with FLAG_PATHLENGTH: partial path lengths (Engine.set_partial_paths)
+FLAG_PARTIAL_PATHS = 1 << 10
 
 # smcrt_scene_deposit_regime
 DEPOSIT_ATOMIC, DEPOSIT_SORTED, DEPOSIT_BUCKETS = 0, 1, 2
@@ -72,6 +74,9 @@ DEPOSIT_REGIMES = {DEPOSIT_ATOMIC: "atomic", DEPOSIT_SORTED: "sorted", DEPOSIT_B
 
 # smcrt_detector.reserved, bit 0: the detector files the photon's path at every hit it scores
 DET_TRACK_HISTORY = 1
+
+# partial path lengths: the most media a tracked scene may have (SMCRT_PPATH_MAX_MEDIA)
+PPATH_MAX_MEDIA = 16
 
 # smcrt_phasor_config.reserved, bit 0: a voxel piece adds n * length to the phase (optical path)
 PHASOR_OPTICAL_PATH = 1
@@ -198,6 +203,17 @@ class Path(C.Structure):
                 ("start", C.c_double * 3), ("dir", C.c_double * 3), ("point_sep", C.c_double), ("weight", C.c_double)]
 
 
+class PPathConfig(C.Structure):
+    _fields_ = [("range_first", C.c_uint64), ("range_count", C.c_uint64), ("max_records", C.c_int64),
+                ("reserved", C.c_int64)]
+
+
+class PPath(C.Structure):
+    _fields_ = [("photon", C.c_uint64), ("detector", C.c_int32), ("hit", C.c_uint32), ("status", C.c_uint32),
+                ("layer", C.c_int32), ("nscatt", C.c_uint32), ("reserved", C.c_int32),
+                ("start", C.c_double * 3), ("dir", C.c_double * 3), ("point_sep", C.c_double), ("weight", C.c_double)]
+
+
 class PhasorConfig(C.Structure):
     _fields_ = [("fixed_k", C.c_int32), ("reserved", C.c_int32), ("wavenumber", C.c_double)]
 
@@ -213,6 +229,14 @@ def path_dtype():
     return np.dtype([("photon", "<u8"), ("detector", "<i4"), ("hit", "<u4"), ("n_vertices", "<u4"),
                      ("n_stored", "<u4"), ("status", "<u4"), ("layer", "<i4"), ("offset", "<i8"),
                      ("start", "<f8", 3), ("dir", "<f8", 3), ("point_sep", "<f8"), ("weight", "<f8")])
+
+
+# smcrt_ppath as a numpy dtype (same layout)
+def ppath_dtype():
+    import numpy as np
+    return np.dtype([("photon", "<u8"), ("detector", "<i4"), ("hit", "<u4"), ("status", "<u4"), ("layer", "<i4"),
+                     ("nscatt", "<u4"), ("reserved", "<i4"), ("start", "<f8", 3), ("dir", "<f8", 3),
+                     ("point_sep", "<f8"), ("weight", "<f8")])
 
 
 # photon record as a numpy dtype (same layout)
@@ -295,4 +319,5 @@ EXPORTED_SYMBOLS = [
     "smcrt_displacement_compile", "smcrt_displacement_eval", "smcrt_displacement_describe",
     "smcrt_voxel_scene_create", "smcrt_scene_deposit_regime",
     "smcrt_mesh_scene_create",
+    "smcrt_scene_set_partial_paths", "smcrt_scene_partial_path_counts", "smcrt_scene_read_partial_paths",
 ]

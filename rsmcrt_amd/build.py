@@ -42,7 +42,10 @@ UNITS = [(src, ()) for src in SOURCES] + [
     (KINST, (f"-DKI_F={f}", f"-DKI_G={g}", f"-DKI_P={p}") + (PLAIN_WS_FLAGS if p == 5 else ()))
     for f in (0, 1) for g in (0, 1, 2) for p in (5, 6)] + [
     # part 7: mesh_kernel (mesh.h: closed triangle surfaces; its faces are always staged in LDS)
-    (KINST, ("-DKI_F=0", f"-DKI_G={g}", "-DKI_P=7")) for g in (0, 1, 2)]
+    (KINST, ("-DKI_F=0", f"-DKI_G={g}", "-DKI_P=7")) for g in (0, 1, 2)] + [
+    # parts 8 and 9: the PPL instantiations of voxel_kernel and of mesh_kernel (the partial path
+    # lengths, ppath.h), in units of their own so that parts 4 and 7 stay the objects they were
+    (KINST, ("-DKI_F=0", f"-DKI_G={g}", f"-DKI_P={p}")) for g in (0, 1, 2) for p in (8, 9)]
 DEPS = SOURCES + [KINST] + sorted(glob.glob(os.path.join(PKG, "csrc", "*.h"))) + [os.path.join(ROOT, "include", "smcrt.h")]
 ARCH = os.environ.get("SMCRT_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=off: no fused multiply-add, so fp64 trajectories are bit-identical to the

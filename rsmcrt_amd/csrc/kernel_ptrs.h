@@ -6,7 +6,8 @@
 // transport_kernel's HIST instantiations, the photon path recorder of paths.h; part 3, F = 0
 // only: its PHAS instantiations, the phasor tally of phasor.h; part 4, F = 0 only: voxel_kernel,
 // the label-volume transport of voxel.h; part 7, F = 0 only: mesh_kernel, the triangle-surface
-// transport of mesh.h), so
+// transport of mesh.h; parts 8 and 9, F = 0 only: the PPL instantiations of voxel_kernel and of
+// mesh_kernel, the partial path lengths of ppath.h), so
 // the instantiations of transport_kernel and ws_kernel (kernels.h, ws.h) build in parallel
 // instead of in one translation unit. Each object exports these getters; hipLaunchKernel and
 // the occupancy query take the host stub that kernel_ptr returns for a launch choice.
@@ -67,6 +68,15 @@ SMCRT_KINST_MESH_DECL(0)
 SMCRT_KINST_MESH_DECL(1)
 SMCRT_KINST_MESH_DECL(2)
 #undef SMCRT_KINST_MESH_DECL
+#define SMCRT_KINST_PPL_DECL(G)                    \
+  const void* kinst_voxel_ppl_0_##G(int xsrc);     \
+  const void* kinst_mesh_ppl_0_##G(int xsrc);      \
+  void kinst_diagvp_0_##G(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6); \
+  void kinst_diagmp_0_##G(unsigned long long* d72, unsigned long long* t9, unsigned long long* c6);
+SMCRT_KINST_PPL_DECL(0)
+SMCRT_KINST_PPL_DECL(1)
+SMCRT_KINST_PPL_DECL(2)
+#undef SMCRT_KINST_PPL_DECL
 
 // transport_kernel<lds_faces, gm, xsrc, coop, hist, phas>; the general emitter with the COOP
 // machinery (xsrc && coop), the path recorder (hist, paths.h) and the phasor tally (phas,
@@ -89,14 +99,16 @@ inline const void* transport_kernel_ptr(bool lds_faces, int gm, bool xsrc, bool 
     default: return kinst_transport_1_2(x, c);
   }
 }
-// voxel_kernel<gm, xsrc> (voxel.h)
-inline const void* voxel_kernel_ptr(int gm, bool xsrc) {
+// voxel_kernel<gm, xsrc, ppl> (voxel.h)
+inline const void* voxel_kernel_ptr(int gm, bool xsrc, bool ppl = false) {
   const int x = xsrc ? 1 : 0;
+  if (ppl) return gm == 0 ? kinst_voxel_ppl_0_0(x) : gm == 1 ? kinst_voxel_ppl_0_1(x) : kinst_voxel_ppl_0_2(x);
   return gm == 0 ? kinst_voxel_0_0(x) : gm == 1 ? kinst_voxel_0_1(x) : kinst_voxel_0_2(x);
 }
-// mesh_kernel<gm, xsrc> (mesh.h)
-inline const void* mesh_kernel_ptr(int gm, bool xsrc) {
+// mesh_kernel<gm, xsrc, ppl> (mesh.h)
+inline const void* mesh_kernel_ptr(int gm, bool xsrc, bool ppl = false) {
   const int x = xsrc ? 1 : 0;
+  if (ppl) return gm == 0 ? kinst_mesh_ppl_0_0(x) : gm == 1 ? kinst_mesh_ppl_0_1(x) : kinst_mesh_ppl_0_2(x);
   return gm == 0 ? kinst_mesh_0_0(x) : gm == 1 ? kinst_mesh_0_1(x) : kinst_mesh_0_2(x);
 }
 // ws_kernel<lds_faces, gm, xf, slots, iv, tk> (xf: the Fresnel/detector program points; slots 2 or
@@ -117,8 +129,8 @@ inline const void* ws_kernel_ptr(bool lds_faces, int gm, bool xf, int slots, boo
 inline const void* kernel_ptr(const LaunchChoice& c) {
   switch (c.family) {
     case KF_WS: return ws_kernel_ptr(c.lds_faces, c.gm, c.xf, c.slots, c.iv, c.tk);
-    case KF_VOXEL: return voxel_kernel_ptr(c.gm, c.xsrc);
-    case KF_MESH: return mesh_kernel_ptr(c.gm, c.xsrc);
+    case KF_VOXEL: return voxel_kernel_ptr(c.gm, c.xsrc, c.ppl);
+    case KF_MESH: return mesh_kernel_ptr(c.gm, c.xsrc, c.ppl);
     default: return transport_kernel_ptr(c.lds_faces, c.gm, c.xsrc, c.coop, c.hist, c.phas);
   }
 }
@@ -140,6 +152,8 @@ inline void kinst_diag_gather(unsigned long long* d72, unsigned long long* t9, u
   kinst_diagf_0_0(d72, t9, c6); kinst_diagf_0_1(d72, t9, c6); kinst_diagf_0_2(d72, t9, c6);
   kinst_diagv_0_0(d72, t9, c6); kinst_diagv_0_1(d72, t9, c6); kinst_diagv_0_2(d72, t9, c6);
   kinst_diagm_0_0(d72, t9, c6); kinst_diagm_0_1(d72, t9, c6); kinst_diagm_0_2(d72, t9, c6);
+  kinst_diagvp_0_0(d72, t9, c6); kinst_diagvp_0_1(d72, t9, c6); kinst_diagvp_0_2(d72, t9, c6);
+  kinst_diagmp_0_0(d72, t9, c6); kinst_diagmp_0_1(d72, t9, c6); kinst_diagmp_0_2(d72, t9, c6);
 }
 
 }  // namespace smcrt

@@ -1,6 +1,6 @@
 // kinst.hip — one (LDS faces, grid mode) slice of the transport kernel instantiations.
-// Compiled thirty-six times by build.py (-DKI_F=0/1 -DKI_G=0/1/2 -DKI_P=0/1/5/6, and -DKI_P=2, 3,
-// 4 and 7 with -DKI_F=0); see kernel_ptrs.h.
+// Compiled forty-two times by build.py (-DKI_F=0/1 -DKI_G=0/1/2 -DKI_P=0/1/5/6, and -DKI_P=2, 3,
+// 4, 7, 8 and 9 with -DKI_F=0); see kernel_ptrs.h.
 // Part 0 holds transport_kernel and the XF ws_kernel, part 1 the plain ws_kernel (the lean path
 // of M1), which build.py compiles with its own scheduler flags (see UNITS there), part 2 the
 // HIST instantiations of transport_kernel (the photon path recorder, paths.h; faces in device
@@ -11,17 +11,19 @@
 // plain ones (5, with part 1's scheduler flags) and the XF ones (6, with part 0's), in units of
 // their own so that they build beside the others.
 // Part 7 holds mesh_kernel (mesh.h: closed triangle surfaces, no SDF), plain and general emitter.
+// Parts 8 and 9 hold the PPL instantiations of voxel_kernel and of mesh_kernel (the partial path
+// lengths, ppath.h), in units of their own so that parts 4 and 7 stay the objects they were.
 #include "kernels.h"
 #include "kernel_ptrs.h"
-#if defined(KI_P) && KI_P == 4
+#if defined(KI_P) && (KI_P == 4 || KI_P == 8)
 #include "voxel.h"
 #endif
-#if defined(KI_P) && KI_P == 7
+#if defined(KI_P) && (KI_P == 7 || KI_P == 9)
 #include "mesh.h"
 #endif
 
 #if !defined(KI_F) || !defined(KI_G) || !defined(KI_P)
-#error "kinst.hip is compiled with -DKI_F=<0|1> -DKI_G=<0|1|2> -DKI_P=<0|1|2|3|4|5|6|7> (rsmcrt_amd/build.py)"
+#error "kinst.hip is compiled with -DKI_F=<0|1> -DKI_G=<0|1|2> -DKI_P=<0|1|2|3|4|5|6|7|8|9> (rsmcrt_amd/build.py)"
 #endif
 #define KI_NAME3(a, f, g) a##_##f##_##g
 #define KI_NAME2(a, f, g) KI_NAME3(a, f, g)
@@ -29,7 +31,23 @@
 
 namespace smcrt {
 
-#if KI_P == 7
+#if KI_P == 9
+#if KI_F != 0
+#error "mesh_kernel's PPL instantiations (KI_P=9) are compiled with KI_F=0 only (its faces are always staged in LDS)"
+#endif
+const void* KI_NAME(kinst_mesh_ppl)(int xsrc) {
+  return xsrc ? (const void*)mesh_kernel<KI_G, true, true> : (const void*)mesh_kernel<KI_G, false, true>;
+}
+#define KI_DIAG_NAME KI_NAME(kinst_diagmp)
+#elif KI_P == 8
+#if KI_F != 0
+#error "voxel_kernel's PPL instantiations (KI_P=8) are compiled with KI_F=0 only (its faces are always staged in LDS)"
+#endif
+const void* KI_NAME(kinst_voxel_ppl)(int xsrc) {
+  return xsrc ? (const void*)voxel_kernel<KI_G, true, true> : (const void*)voxel_kernel<KI_G, false, true>;
+}
+#define KI_DIAG_NAME KI_NAME(kinst_diagvp)
+#elif KI_P == 7
 #if KI_F != 0
 #error "mesh_kernel (KI_P=7) is compiled with KI_F=0 only (its faces are always staged in LDS)"
 #endif

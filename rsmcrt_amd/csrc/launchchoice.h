@@ -8,7 +8,7 @@
 namespace smcrt {
 
 enum KernelFamily : int { KF_TRANSPORT, KF_WS, KF_VOXEL, KF_MESH };
-constexpr int GRID_KEY_WS = 8, N_GRID_KEYS = 9;
+constexpr int GRID_KEY_WS = 8, GRID_KEY_PPL = 9, N_GRID_KEYS = 11;
 struct LaunchChoice {
   KernelFamily family = KF_TRANSPORT;
   // the family's template coordinates as kernel_ptrs.h takes them (the others stay 0)
@@ -18,11 +18,13 @@ struct LaunchChoice {
   bool coop = false, hist = false, phas = false;  // transport_kernel
   bool xf = false, iv = false, tk = false;        // ws_kernel
   int slots = 0;
+  bool ppl = false;  // voxel_kernel, mesh_kernel: the partial path lengths (ppath.h), with their rows of LDS
   bool scr = false;  // a PHAS launch that tallies field screens: no coordinate, a fourth start-point row of LDS
   size_t lds = 0;    // dynamic LDS bytes
   // Launches of a scene with equal keys run the same kernel with the same block and LDS, up to
   // ws_kernel's TK (same block, same LDS, same register cap): they share a persistent grid.
   int grid_key() const {
+    if (ppl) return GRID_KEY_PPL + (xsrc ? 1 : 0);
     return family == KF_WS ? GRID_KEY_WS : 2 * (hist ? 1 : scr ? 3 : phas ? 2 : 0) + (xsrc ? 1 : 0);
   }
 };

@@ -20,9 +20,14 @@
 // can still wait on the counters of that trip's deposit stores and atomics (voxel.h); how much they
 // do has not been measured.
 //
-// Included by kinst.hip's part 7 only (after kernels.h), so no other kernel sees this file.
+// PPL: the partial path lengths (ppath.h, SMCRT_FLAG_PARTIAL_PATHS), as in voxel_kernel: every
+// line of it is under `if constexpr (PPL)` and the lane's state is an empty type otherwise, so the
+// other instantiations are what they were without it.
+//
+// Included by kinst.hip's parts 7 and 9 only (after kernels.h), so no other kernel sees this file.
 #pragma once
 #include "kernels.h"
+#include "ppath.h"
 
 namespace smcrt {
 
@@ -43,7 +48,7 @@ enum : uint32_t {
   MS_DONE,      // photon finished: tallies, record, next photon
 };
 
-template <int GM, bool XSRC>
+template <int GM, bool XSRC, bool PPL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES_PER_EU_MESH))) void mesh_kernel(
     KParams K, const smcrt_sdf_node* __restrict__ nodes, const ProgOp* __restrict__ prog,
     const smcrt_detector* __restrict__ dets, const int64_t* __restrict__ det_off, const KCold* __restrict__ C) {
@@ -62,6 +67,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
   DepositState D;
   D.init(K, C, sh_dyn + M.doubles);
   zero_counters(sh);
+  // PPL: this photon's length in every medium, in LDS after the deposit words (ppath.h). An empty
+  // type otherwise.
+  [[maybe_unused]] std::conditional_t<PPL, PplLane, NoPplLane> P;
+  if constexpr (PPL) {
+    ppl_init(C, P);
+    ppl_clear(P, sh_dyn);
+  }
   __syncthreads();
 
   const MeshNode* __restrict__ const bvh = C->mesh_nodes;
@@ -92,7 +104,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
       bool dep = false;
       uint32_t vox = 0;
       double val = 0.0;
-      if (walk) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight);
+      if constexpr (PPL) {  // the piece the tally sees, unrounded, in the leg's medium
+        DdaPiece pc;
+        if (walk) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight, &pc);
+        if (walk && dep) ppl_add(P, sh_dyn, L.layer, pc.dc);
+      } else {
+        if (walk) dda_step<GM>(K, L, L.dir, xf, yf, zf, dep, vox, val, L.weight);
+      }
       D.file(K, C, dep, vox, val);
       if (walk && !L.seg) L.st = MS_LEGEND;
     }
@@ -108,8 +126,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
         if (L.tflag && pathlen) end = v3(L.old.x - K.xmax, L.old.y - K.ymax, L.old.z - K.zmax);
         if (K.n_dets) {
           const double sep = pointsep(end, L.pos);
-          if (sep < __builtin_huge_val())  // (a leg to infinity without a walk has no end to measure to)
-            LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, L.pos, L.dir, sep, L.layer, L.weight);
+          if (sep < __builtin_huge_val()) {  // (a leg to infinity without a walk has no end to measure to)
+            if constexpr (PPL) {  // every hit files the lengths up to the end of the leg
+              auto file = [&](int32_t di, const smcrt_detector*) {
+                ppl_file(C, P, sh_dyn, ((uint64_t)L.rng.pid_hi << 32) | L.rng.pid_lo, di, 0u, L.pos, L.dir, sep, L.layer, L.weight,
+                         LU(LU_NSCATT));
+              };
+              LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, L.pos, L.dir, sep, L.layer, L.weight, nullptr, file);
+            } else {
+              LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, L.pos, L.dir, sep, L.layer, L.weight);
+            }
+          }
         }
         L.pos = end;
         if (L.tflag) L.st = MS_DONE;  // escaped
@@ -155,6 +182,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
         }
         if (L.st == MS_EMIT) {  // (no medium until the first cast)
           const bool ok = emit_event<GM, XSRC>(K, C, L, sh);
+          if constexpr (PPL) ppl_clear(P, sh_dyn);  // a new photon (a faulted emission files zeros)
           if (ok) L.pend = true;
           L.st = ok ? MS_FLIGHT : MS_DONE;
         }
@@ -198,6 +226,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
         if (L.st == MS_DONE) {  // photon finished
           close_photon(L, sh);
           write_record(K, C, L, sh, L.pos);
+          if constexpr (PPL) {  // the range trigger: the final lengths of a photon of the tracked range
+            const uint64_t pid = ((uint64_t)L.rng.pid_hi << 32) | L.rng.pid_lo;
+            if (pid - C->range_first < C->range_count)
+              ppl_file(C, P, sh_dyn, pid, -1, LU(LU_STATUS), L.pos, L.dir, 0.0, L.layer, L.weight, LU(LU_NSCATT));
+          }
           L.tflag = false; L.fault = false; L.pend = false; L.seg = false;
           L.st = MS_FETCH;
         }

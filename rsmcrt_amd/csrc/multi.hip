@@ -457,6 +457,8 @@ static int accumulate_locked(smcrt_multi* m, const smcrt_source* src, const smcr
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
   if (cfg->flags & SMCRT_FLAG_PHASOR)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PHASOR: the phasor grid is tallied by smcrt_run only");
+  if (cfg->flags & SMCRT_FLAG_PARTIAL_PATHS)  // (smcrt_multi_* holds SDF scenes only; the arena belongs to one scene)
+    return fail(SMCRT_ERR_UNSUPPORTED, "SMCRT_FLAG_PARTIAL_PATHS: smcrt_multi_* records no partial path lengths (use smcrt_run)");
   if (cfg->flags & SMCRT_FLAG_RECORD_PHOTONS)
     return fail(SMCRT_ERR_INVALID_ARG, "photon records are not kept by the multi-GPU path (use smcrt_run)");
   const size_t n = m->devices.size();

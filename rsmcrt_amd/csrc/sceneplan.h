@@ -274,19 +274,31 @@ inline bool ws_invoxel_on(int knob, bool xf) { return knob < 0 ? !xf : knob != 0
 // points, and the lane scratch that goes with it)
 inline bool plan_xf(const ScenePlan& p) { return p.fresnel || p.n_dets > 0; }
 
+// Partial path lengths (ppath.h): a scene of at most this many media can be tracked, and the LDS
+// of a tracking launch after its deposit words: one double per medium and lane of the 256-thread block.
+constexpr int32_t PPL_MAX_MEDIA = SMCRT_PPATH_MAX_MEDIA;
+inline size_t ppl_lds_bytes(const ScenePlan& p) { return (size_t)p.n_top * 256 * sizeof(double); }
+// the static LDS of voxel_kernel and mesh_kernel: their LaneCounters (transport.h)
+constexpr size_t SDFLESS_STATIC_LDS = sizeof(LaneCounters);
+
 // ---- the launch choice (launchchoice.h): which compiled kernel a launch runs, and with what LDS ----
 // The choice for one launch of plan p: `xsrc` the general emitter, `bucket_tiles` the launch's
 // KParams::bucket_tiles, `flags` the run's, and the scene state that matters: path tracking and
 // the phasor tally configured, the number of field screens. (`lean_ok` false, or no bucket
 // tiles, never gives ws_kernel: what a scene's transport_kernel grids are sized with.)
+// `ppl_lds`: the bytes of LDS that partial path lengths are configured with on a voxel or a mesh
+// scene (ppl_lds_bytes), 0 when they are not; a run with SMCRT_FLAG_PARTIAL_PATHS then takes the
+// PPL instantiation and that much LDS after the deposit words.
 inline LaunchChoice launch_choice(const ScenePlan& p, bool lean_ok, bool xsrc, uint32_t bucket_tiles, uint32_t flags,
-                                  bool path_on, bool phasor_on, size_t n_screens) {
+                                  bool path_on, bool phasor_on, size_t n_screens, size_t ppl_lds = 0) {
   LaunchChoice c;
   c.gm = p.grid_mode;
   if (p.voxel || p.mesh) {  // (neither has a lean path, a path recorder or a phasor tally)
     c.family = p.mesh ? KF_MESH : KF_VOXEL;
     c.xsrc = xsrc;
     c.lds = p.face_bytes + (size_t)dep_words(p) * sizeof(uint32_t);  // (voxel.h, mesh.h: media + faces, then the deposit words)
+    c.ppl = (flags & SMCRT_FLAG_PARTIAL_PATHS) && ppl_lds > 0;
+    if (c.ppl) c.lds += ppl_lds;  // (ppath.h: then len[medium][lane])
   } else if (launch_lean(lean_ok, xsrc, bucket_tiles, flags)) {
     c.family = KF_WS;
     c.lds_faces = p.lds_faces;

@@ -181,6 +181,13 @@ struct smcrt_scene : ScenePlan {
   DevBuf<smcrt_path> d_path_headers;
   DevBuf<unsigned long long> d_path_ctl;
   uint64_t hist_lanes = 0;
+  // partial path lengths (smcrt_scene_set_partial_paths; ppath.h): the arena of ppath_cfg.max_records
+  // slots of n_top doubles with its headers, and the counters [claimed, dropped]
+  bool ppath_on = false;
+  smcrt_ppath_config ppath_cfg{};
+  DevBuf<double> d_ppl_lengths;
+  DevBuf<smcrt_ppath> d_ppl_headers;
+  DevBuf<unsigned long long> d_ppl_ctl;
   // the phasor tally (smcrt_scene_set_phasor; phasor.h): the grid, 2 doubles per voxel
   bool phasor_on = false;
   smcrt_phasor_config phasor_cfg{};
@@ -544,6 +551,18 @@ int smcrt::scene_needs_sdf(const smcrt_scene* s, const char* what) {
                                                                   : " is not supported on mesh scenes (smcrt_mesh_scene_create)"));
 }
 
+// The LDS that a launch with partial path lengths adds on this scene (launch_choice's ppl_lds): 0
+// while they are not configured.
+static size_t ppl_lds_of(const smcrt_scene* s) { return s->ppath_on ? ppl_lds_bytes(*s) : 0; }
+
+// SMCRT_FLAG_PARTIAL_PATHS needs a voxel or a mesh scene (ppath.h: transport_kernel and ws_kernel
+// have no accumulator).
+static int ppl_flag_scene_ok(const smcrt_scene* s, uint32_t flags) {
+  if (!(flags & SMCRT_FLAG_PARTIAL_PATHS) || s->voxel || s->mesh) return SMCRT_OK;
+  return fail(SMCRT_ERR_UNSUPPORTED, "SMCRT_FLAG_PARTIAL_PATHS is not supported on SDF scenes (smcrt_scene_create): "
+                                     "partial path lengths are kept by voxel and mesh scenes only");
+}
+
 // The run flags a voxel or a mesh scene has no code for (voxel.h, mesh.h).
 static int sdfless_flags_ok(const smcrt_scene* s, uint32_t flags) {
   if (!s->voxel && !s->mesh) return SMCRT_OK;
@@ -828,7 +847,8 @@ static int diag_report(hipStream_t stream, bool lean) {
 
 // One launch: the transport kernel on `stream`, then its fold on s->fstream.
 static int launch_one(smcrt_scene* s, const KParams& K, const KCold& Ch, bool xsrc, hipStream_t stream, int sl, int qi) {
-  const LaunchChoice c = launch_choice(*s, s->lean_ok, xsrc, K.bucket_tiles, K.flags, s->path_on, s->phasor_on, s->screens.size());
+  const LaunchChoice c = launch_choice(*s, s->lean_ok, xsrc, K.bucket_tiles, K.flags, s->path_on, s->phasor_on, s->screens.size(),
+                                       ppl_lds_of(s));
   Event* ev = nullptr;
   int st = enqueue_transport(s, K, Ch, c, stream, sl, qi, &ev);
   if (!st) st = enqueue_fold(s, K, Ch.jmean, stream, sl, ev);
@@ -894,8 +914,17 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.path_ctl = hist ? (unsigned long long*)s->d_path_ctl : nullptr;
   Ch.hist_lanes = hist ? s->hist_lanes : 0;
   Ch.path_max = hist ? (uint64_t)s->path_cfg.max_paths : 0;
-  Ch.range_first = hist ? s->path_cfg.range_first : 0;
-  Ch.range_count = hist ? s->path_cfg.range_count : 0;
+  const bool ppl = run.ppl;
+  Ch.range_first = hist ? s->path_cfg.range_first : ppl ? s->ppath_cfg.range_first : 0;
+  Ch.range_count = hist ? s->path_cfg.range_count : ppl ? s->ppath_cfg.range_count : 0;
+  // partial path lengths: the arena, and where the lanes' lengths start in the launch's LDS (what
+  // launch_choice sizes it with: media and faces, then the plan's deposit words)
+  Ch.ppl_lengths = ppl ? (double*)s->d_ppl_lengths : nullptr;
+  Ch.ppl_headers = ppl ? (smcrt_ppath*)s->d_ppl_headers : nullptr;
+  Ch.ppl_ctl = ppl ? (unsigned long long*)s->d_ppl_ctl : nullptr;
+  Ch.ppl_max = ppl ? (uint64_t)s->ppath_cfg.max_records : 0;
+  Ch.ppl_lds_off = ppl ? (uint32_t)((s->face_bytes + (size_t)dep_words(*s) * sizeof(uint32_t)) / sizeof(double)) : 0u;
+  Ch.ppl_n_media = ppl ? (uint32_t)s->n_top : 0u;
   Ch.hist_max_vertices = hist ? (uint32_t)s->path_cfg.max_vertices : 0;
   // the phasor tally: the wavenumber of photons that sample no wavelength of their own is the
   // fixed one, or 2 pi / the constant spectrum's value (NULL spectrum: 500.0, smcrt.h)
@@ -957,6 +986,7 @@ static int launch(smcrt_scene* s, const smcrt_source* src, const smcrt_run_confi
     if (!s->d_vs_cdf)
       return fail(SMCRT_ERR_INVALID_ARG, "a volume source needs smcrt_scene_set_volume_source first (the scene holds no table)");
   }
+  if (const int pst = ppl_flag_scene_ok(s, cfg->flags)) return pst;  // (every driver ends here)
   if (cfg->n_photons == 0) return SMCRT_OK;
   // sources other than point/uniform/pencil, a sampled spectrum or batched origins: the
   // general emitter
@@ -999,7 +1029,8 @@ static int launch(smcrt_scene* s, const smcrt_source* src, const smcrt_run_confi
   KParams K;
   KCold Ch;
   // (hist, phas and scr are those of every batch: a batch that runs ws_kernel has none of the three)
-  const LaunchChoice run = launch_choice(*s, false, xsrc, 0, cfg->flags, s->path_on, s->phasor_on, s->screens.size());
+  const LaunchChoice run = launch_choice(*s, false, xsrc, 0, cfg->flags, s->path_on, s->phasor_on, s->screens.size(),
+                                         ppl_lds_of(s));
   if (const int st = fill_params(s, src, cfg, dt, plan, stream, !orun, run, K, Ch)) return st;
   const bool binned = launch_binned(*s, dt.jmean != nullptr, cfg->flags);
   const bool overlap = (cfg->flags & SMCRT_FLAG_OVERLAP) != 0;
@@ -1080,10 +1111,13 @@ int smcrt_run_device(smcrt_scene* s, const smcrt_source* src, const smcrt_run_co
   g_last_error.clear();
   if (!s || !src || !cfg || !dev) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
   if (const int vst = sdfless_flags_ok(s, cfg->flags)) return vst;
+  if (const int pst = ppl_flag_scene_ok(s, cfg->flags)) return pst;
   if (cfg->flags & SMCRT_FLAG_TRACK_PATHS)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
   if (cfg->flags & SMCRT_FLAG_PHASOR)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PHASOR: the phasor grid is tallied by smcrt_run only");
+  if (cfg->flags & SMCRT_FLAG_PARTIAL_PATHS)
+    return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PARTIAL_PATHS: partial path lengths are recorded by smcrt_run only");
   std::lock_guard<std::mutex> g(s->mu);
   HIPCHK(hipSetDevice(s->device));
   return launch(s, src, cfg, *dev, (hipStream_t)stream);
@@ -1162,7 +1196,13 @@ int smcrt_run(smcrt_scene* s, const smcrt_source* src, const smcrt_run_config* c
   g_last_error.clear();
   if (!s || !src || !cfg || !io) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
   if (const int vst = sdfless_flags_ok(s, cfg->flags)) return vst;
+  if (const int pst = ppl_flag_scene_ok(s, cfg->flags)) return pst;
   std::lock_guard<std::mutex> g(s->mu);
+  const bool ppl = (cfg->flags & SMCRT_FLAG_PARTIAL_PATHS) != 0;
+  if (ppl && !(cfg->flags & SMCRT_FLAG_PATHLENGTH))
+    return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PARTIAL_PATHS needs SMCRT_FLAG_PATHLENGTH (the lengths are those of the voxel walk)");
+  if (ppl && !s->ppath_on)
+    return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PARTIAL_PATHS needs smcrt_scene_set_partial_paths first");
   const bool track = (cfg->flags & SMCRT_FLAG_TRACK_PATHS) != 0;
   if (track && !s->path_on)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS needs smcrt_scene_set_path_tracking first");
@@ -1175,6 +1215,7 @@ int smcrt_run(smcrt_scene* s, const smcrt_source* src, const smcrt_run_config* c
   HIPCHK(hipSetDevice(s->device));
   if (track)  // a tracking run starts with an empty arena
     HIPCHK(hipMemsetAsync(s->d_path_ctl, 0, 3 * sizeof(unsigned long long), s->stream));
+  if (ppl) HIPCHK(hipMemsetAsync(s->d_ppl_ctl, 0, 2 * sizeof(unsigned long long), s->stream));  // likewise
   return run_sync(s, src, cfg, io, nullptr);
 }
 
@@ -1190,6 +1231,7 @@ int smcrt_run_origins(smcrt_scene* s, const smcrt_source* src, const double* ori
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_TRACK_PATHS: paths are recorded by smcrt_run only");
   if (cfg->flags & SMCRT_FLAG_PHASOR)
     return fail(SMCRT_ERR_INVALID_ARG, "SMCRT_FLAG_PHASOR: the phasor grid is tallied by smcrt_run only");
+  if (const int pst = ppl_flag_scene_ok(s, cfg->flags)) return pst;
   if (cfg->flags & SMCRT_FLAG_RECORD_PHOTONS) return fail(SMCRT_ERR_INVALID_ARG, "photon records are not kept for batched origins");
   if (n_origins > 0xFFFFFFFFll) return fail(SMCRT_ERR_INVALID_ARG, "more than 2^32 origins");
   if (n_origins == 0 || cfg->n_photons == 0) return SMCRT_OK;
@@ -1481,6 +1523,119 @@ int smcrt_scene_read_paths(smcrt_scene* s, smcrt_path* paths, double* vertices) 
     paths[k].offset = off;
     std::memcpy(vertices + 4 * off, arena.data() + slot * mv * 4, (size_t)hdr[slot].n_stored * 4 * sizeof(double));
     off += hdr[slot].n_stored;
+  }
+  return SMCRT_OK;
+}
+
+// ---- partial path lengths (ppath.h) ------------------------------------------------------
+static void release_ppaths(smcrt_scene* s) {
+  s->ppath_on = false;
+  s->d_ppl_lengths.reset(); s->d_ppl_headers.reset(); s->d_ppl_ctl.reset();
+}
+
+// The three entry points serve voxel and mesh scenes only.
+static int ppaths_scene_ok(const smcrt_scene* s) {
+  if (s->voxel || s->mesh) return SMCRT_OK;
+  return fail(SMCRT_ERR_UNSUPPORTED, "partial path lengths are not supported on SDF scenes (smcrt_scene_create): "
+                                     "they are kept by voxel and mesh scenes only");
+}
+
+int smcrt_scene_set_partial_paths(smcrt_scene* s, const smcrt_ppath_config* cfg) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  if (const int vst = ppaths_scene_ok(s)) return vst;
+  uint64_t mr = 0;
+  const uint64_t nm = (uint64_t)s->n_top;
+  if (cfg) {  // (decided before any device call)
+    if (cfg->max_records < 1) return fail(SMCRT_ERR_INVALID_ARG, "partial path lengths: max_records must be >= 1");
+    if (cfg->reserved != 0) return fail(SMCRT_ERR_INVALID_ARG, "partial path lengths: reserved must be 0");
+    if (cfg->range_count > UINT64_MAX - cfg->range_first)
+      return fail(SMCRT_ERR_INVALID_ARG, "partial path lengths: the photon range overflows");
+    if (s->n_top > PPL_MAX_MEDIA)
+      return fail(SMCRT_ERR_UNSUPPORTED, "partial path lengths: the scene has " + std::to_string(s->n_top) +
+                                             " media, more than the cap of " + std::to_string(PPL_MAX_MEDIA) +
+                                             " (SMCRT_PPATH_MAX_MEDIA: the lengths live in the kernels' LDS)");
+    // a block's LDS with the lengths: what launch_choice asks for, next to the kernels' counters
+    const size_t lds = launch_choice(*s, false, false, 0, SMCRT_FLAG_PATHLENGTH | SMCRT_FLAG_PARTIAL_PATHS, false, false, 0,
+                                     ppl_lds_bytes(*s)).lds + SDFLESS_STATIC_LDS;
+    if (lds > LDS_BYTES)
+      return fail(SMCRT_ERR_UNSUPPORTED, "partial path lengths: a block would need " + std::to_string(lds) +
+                                             " bytes of LDS, more than " + std::to_string(LDS_BYTES));
+    mr = (uint64_t)cfg->max_records;
+    if (mr > (1ull << 40) / (nm * sizeof(double) + sizeof(smcrt_ppath)))
+      return fail(SMCRT_ERR_OOM, "partial path lengths: the arena does not fit");
+  }
+  std::lock_guard<std::mutex> g(s->mu);
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));  // (no launch of this scene may still use the buffers)
+  release_ppaths(s);
+  if (!cfg) return SMCRT_OK;
+  int st;
+  if ((st = dalloc(s->d_ppl_lengths, (size_t)(mr * nm))) || (st = dalloc(s->d_ppl_headers, (size_t)mr)) ||
+      (st = dalloc(s->d_ppl_ctl, 2))) {
+    (void)hipGetLastError();
+    release_ppaths(s);
+    return st;
+  }
+  HIPCHK(hipMemset(s->d_ppl_ctl, 0, 2 * sizeof(unsigned long long)));
+  s->ppath_cfg = *cfg;
+  s->ppath_on = true;
+  // (the tracking launches' persistent grids: asked for once, here)
+  for (int x = 0; x < 2; ++x)
+    (void)blocks_for(s, launch_choice(*s, false, x == 1, 0, SMCRT_FLAG_PATHLENGTH | SMCRT_FLAG_PARTIAL_PATHS, false, false, 0,
+                                      ppl_lds_of(s)));
+  return SMCRT_OK;
+}
+
+// The arena's counters and headers (the used slots) after the scene's launches. Caller holds s->mu.
+static int fetch_ppaths(smcrt_scene* s, unsigned long long ctl[2], std::vector<smcrt_ppath>& hdr) {
+  if (!s->ppath_on) return fail(SMCRT_ERR_INVALID_ARG, "partial path lengths are not configured on this scene");
+  HIPCHK(hipSetDevice(s->device));
+  HIPCHK(hipStreamSynchronize(s->stream));
+  HIPCHK(hipMemcpy(ctl, s->d_ppl_ctl, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  const uint64_t n = std::min<uint64_t>(ctl[0], (uint64_t)s->ppath_cfg.max_records);
+  hdr.resize((size_t)n);
+  if (n) HIPCHK(hipMemcpy(hdr.data(), s->d_ppl_headers, (size_t)n * sizeof(smcrt_ppath), hipMemcpyDeviceToHost));
+  return SMCRT_OK;
+}
+
+int smcrt_scene_partial_path_counts(smcrt_scene* s, int64_t* n_records, int64_t* n_dropped) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  if (const int vst = ppaths_scene_ok(s)) return vst;
+  std::lock_guard<std::mutex> g(s->mu);
+  unsigned long long ctl[2];
+  std::vector<smcrt_ppath> hdr;
+  if (const int st = fetch_ppaths(s, ctl, hdr)) return st;
+  if (n_records) *n_records = (int64_t)hdr.size();
+  if (n_dropped) *n_dropped = (int64_t)ctl[1];
+  return SMCRT_OK;
+}
+
+int smcrt_scene_read_partial_paths(smcrt_scene* s, smcrt_ppath* headers, double* lengths) {
+  g_last_error.clear();
+  if (!s) return fail(SMCRT_ERR_INVALID_ARG, "scene is NULL");
+  if (const int vst = ppaths_scene_ok(s)) return vst;
+  std::lock_guard<std::mutex> g(s->mu);
+  unsigned long long ctl[2];
+  std::vector<smcrt_ppath> hdr;
+  if (const int st = fetch_ppaths(s, ctl, hdr)) return st;
+  if (hdr.empty()) return SMCRT_OK;
+  if (!headers || !lengths) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  // arena order is whatever the atomics gave: (photon, hit) makes the output deterministic
+  std::vector<size_t> order(hdr.size());
+  for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    if (hdr[a].photon != hdr[b].photon) return hdr[a].photon < hdr[b].photon;
+    if (hdr[a].hit != hdr[b].hit) return hdr[a].hit < hdr[b].hit;
+    return a < b;
+  });
+  const size_t nm = (size_t)s->n_top;
+  std::vector<double> arena(hdr.size() * nm);
+  HIPCHK(hipMemcpy(arena.data(), s->d_ppl_lengths, arena.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < order.size(); ++k) {
+    headers[k] = hdr[order[k]];
+    std::memcpy(lengths + k * nm, arena.data() + order[k] * nm, nm * sizeof(double));
   }
   return SMCRT_OK;
 }

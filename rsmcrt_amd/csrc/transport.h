@@ -137,6 +137,16 @@ struct KCold {
   double vs_total;             // cdf[vs_nvox - 1]
   uint32_t vs_nvox;            // nx * ny * nz
   uint32_t vs_last;            // the largest i with cdf[i] > cdf[i-1]
+  // partial path lengths (SMCRT_FLAG_PARTIAL_PATHS; read by the PPL instantiations of voxel_kernel
+  // and mesh_kernel only, ppath.h; null / 0 otherwise). After the volume source's fields, so that
+  // those stay where they were. The range trigger is range_first / range_count above (a voxel or a
+  // mesh scene has no path recorder to share them with).
+  double* ppl_lengths;         // the arena: [ppl_max][ppl_n_media]
+  smcrt_ppath* ppl_headers;    // [ppl_max]
+  unsigned long long* ppl_ctl; // [0] slots claimed, [1] records dropped
+  uint64_t ppl_max;            // arena slots
+  uint32_t ppl_lds_off;        // doubles of dynamic LDS before the lanes' lengths (media, faces, deposit words)
+  uint32_t ppl_n_media;        // rows of len[m][lane] the launch's LDS holds (== K.n_top)
 };
 
 // watchdog sites (KCold::watchdog bits 0-7; smcrt.hip names them)

@@ -13,9 +13,14 @@
 // Fresnel decision, interaction, completion) run together once enough lanes wait for one. What is
 // here is the kernel's own: the walk stage, the Fresnel wall and the flight start.
 //
-// Included by kinst.hip's part 4 only (after kernels.h), so no other kernel sees this file.
+// PPL: the partial path lengths (ppath.h, SMCRT_FLAG_PARTIAL_PATHS), done as HIST is done in
+// transport_kernel: every line of it is under `if constexpr (PPL)` and the lane's state is an
+// empty type otherwise, so the other instantiations are what they were without it.
+//
+// Included by kinst.hip's parts 4 and 8 only (after kernels.h), so no other kernel sees this file.
 #pragma once
 #include "kernels.h"
+#include "ppath.h"
 
 namespace smcrt {
 
@@ -34,7 +39,7 @@ enum : uint32_t {
   VS_DONE,      // photon finished: tallies, record, next photon
 };
 
-template <int GM, bool XSRC>
+template <int GM, bool XSRC, bool PPL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES_PER_EU_VOXEL))) void voxel_kernel(
     KParams K, const smcrt_sdf_node* __restrict__ nodes, const ProgOp* __restrict__ prog,
     const smcrt_detector* __restrict__ dets, const int64_t* __restrict__ det_off, const KCold* __restrict__ C) {
@@ -54,6 +59,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
   DepositState D;
   D.init(K, C, sh_dyn + M.doubles);
   zero_counters(sh);
+  // PPL: this photon's length in every medium, in LDS after the deposit words (ppath.h). An empty
+  // type otherwise.
+  [[maybe_unused]] std::conditional_t<PPL, PplLane, NoPplLane> P;
+  if constexpr (PPL) {
+    ppl_init(C, P);
+    ppl_clear(P, sh_dyn);
+  }
   __syncthreads();
 
   const uint8_t* __restrict__ const labels = C->vox_labels;
@@ -91,6 +103,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
       const bool entered = walk && pc.wall && !L.tflag;
       uint32_t lab = 0;
       if (entered) lab = labels[lin(K, L.xcell, L.ycell, L.zcell)];
+      if constexpr (PPL) {  // the piece the tally sees, unrounded, in the medium of the voxel being left
+        if (walk && dep) ppl_add(P, sh_dyn, L.layer, pc.dc);
+      }
       dep = dep && pathlen;
       D.file(K, C, dep, vox, val);
       if (walk) {
@@ -128,7 +143,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
     if (K.n_dets && leg_end) {
       const V3 start = v3(L.ssp.x - K.xmax, L.ssp.y - K.ymax, L.ssp.z - K.zmax);
       const V3 end = v3(L.old.x - K.xmax, L.old.y - K.ymax, L.old.z - K.zmax);
-      LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, start, L.dir, pointsep(end, start), L.layer, L.weight);
+      if constexpr (PPL) {  // every hit files the lengths up to where the photon stands
+        const double sep = pointsep(end, start);
+        auto file = [&](int32_t di, const smcrt_detector*) {
+          ppl_file(C, P, sh_dyn, ((uint64_t)L.rng.pid_hi << 32) | L.rng.pid_lo, di, 0u, start, L.dir, sep, L.layer, L.weight,
+                   LU(LU_NSCATT));
+        };
+        LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, start, L.dir, sep, L.layer, L.weight, nullptr, file);
+      } else {
+        LCTR(LC_HITS) += record_hits(K, C->det_bins, dets, det_off, start, L.dir, pointsep(end, start), L.layer, L.weight);
+      }
     }
 
     // ---- events: rare and expensive, run together (events_due, lanekit.h) --------------------
@@ -174,6 +198,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
         }
         if (L.st == VS_EMIT) {
           const bool ok = emit_event<GM, XSRC>(K, C, L, sh);
+          if constexpr (PPL) ppl_clear(P, sh_dyn);  // a new photon (a faulted emission files zeros)
           // the position is carried in corner coordinates from here on
           L.old = v3(L.pos.x + K.xmax, L.pos.y + K.ymax, L.pos.z + K.zmax);
           if (ok) L.layer = (int32_t)labels[lin(K, L.xcell, L.ycell, L.zcell)] + 1;
@@ -191,6 +216,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMCRT_WAVES
         if (L.st == VS_DONE) {  // photon finished
           close_photon(L, sh);
           write_record(K, C, L, sh, v3(L.old.x - K.xmax, L.old.y - K.ymax, L.old.z - K.zmax));
+          if constexpr (PPL) {  // the range trigger: the final lengths of a photon of the tracked range
+            const uint64_t pid = ((uint64_t)L.rng.pid_hi << 32) | L.rng.pid_lo;
+            if (pid - C->range_first < C->range_count)
+              ppl_file(C, P, sh_dyn, pid, -1, LU(LU_STATUS), v3(L.old.x - K.xmax, L.old.y - K.ymax, L.old.z - K.zmax), L.dir, 0.0,
+                       L.layer, L.weight, LU(LU_NSCATT));
+          }
           L.tflag = false; L.fault = false;
           L.st = VS_FETCH;
         }

@@ -109,6 +109,9 @@ def load_library(path: str = LIB_PATH):
         L.smcrt_scene_set_path_tracking.argtypes = [C.c_void_p, C.POINTER(abi.PathConfig)]
         L.smcrt_scene_path_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 4
         L.smcrt_scene_read_paths.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        L.smcrt_scene_set_partial_paths.argtypes = [C.c_void_p, C.POINTER(abi.PPathConfig)]
+        L.smcrt_scene_partial_path_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 2
+        L.smcrt_scene_read_partial_paths.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         L.smcrt_scene_set_phasor.argtypes = [C.c_void_p, C.POINTER(abi.PhasorConfig)]
         L.smcrt_scene_read_phasor.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.smcrt_scene_reset_phasor.argtypes = [C.c_void_p]
@@ -379,6 +382,35 @@ class Engine:
             _check(L.smcrt_scene_read_paths(self._h, hdr.ctypes.data_as(C.c_void_p),
                                             vtx.ctypes.data_as(C.POINTER(C.c_double))))
         return hdr, vtx, counts
+
+    def set_partial_paths(self, range_first=0, range_count=0, max_records=65536):
+        """Configure partial path lengths on a voxel or a mesh scene (smcrt_scene_set_partial_paths):
+        runs made with abi.FLAG_PARTIAL_PATHS | abi.FLAG_PATHLENGTH then file the length in every
+        medium of every photon of [range_first, range_first + range_count) when it finishes, and the
+        lengths so far at every detector hit. `set_partial_paths(None)` turns it off and frees the
+        arena."""
+        if range_first is None:
+            _check(load_library().smcrt_scene_set_partial_paths(self._h, None))
+            return
+        cfg = abi.PPathConfig()
+        cfg.range_first, cfg.range_count, cfg.max_records = int(range_first), int(range_count), int(max_records)
+        _check(load_library().smcrt_scene_set_partial_paths(self._h, C.byref(cfg)))
+
+    def partial_paths(self):
+        """The records of the last tracking run (smcrt_scene_read_partial_paths), sorted by (photon,
+        hit): (headers, lengths, counts). `headers` is a structured array (abi.ppath_dtype()),
+        `lengths` an (n, n_media) array, `counts` holds n_records and n_dropped.
+        rsmcrt_amd.partialpaths turns them into times of flight and reweighted signals."""
+        L = load_library()
+        c = [C.c_int64() for _ in range(2)]
+        _check(L.smcrt_scene_partial_path_counts(self._h, *[C.byref(x) for x in c]))
+        counts = dict(zip(("n_records", "n_dropped"), (x.value for x in c)))
+        hdr = np.zeros(counts["n_records"], dtype=abi.ppath_dtype())
+        lens = np.zeros((counts["n_records"], self.scene.n_media))
+        if len(hdr):
+            _check(L.smcrt_scene_read_partial_paths(self._h, hdr.ctypes.data_as(C.c_void_p),
+                                                    lens.ctypes.data_as(C.POINTER(C.c_double))))
+        return hdr, lens, counts
 
     def set_phasor(self, wavenumber="sampled", optical_path=False):
         """Configure the phasor tally (smcrt_scene_set_phasor): runs made with abi.FLAG_PHASOR then
