@@ -3,7 +3,9 @@ their closed-form expectations (tests/analytic_ref.py) and the statistics that c
 them. Shared by tests/test_analytic_cpu.py and tests/test_gpu_analytic.py, and for the detector
 cases (below the grids') by tests/test_detectors_analytic_cpu.py and
 tests/test_gpu_detectors_analytic.py; runs neither the engine nor the restatements, so that what
-is compared with what stays in the tests.
+is compared with what stays in the tests. The scattering-medium cases (S) and the curved-surface
+cases (D: a glass sphere on this same grid, in SDF, table and mesh form; no voxel form, a label
+volume has no curved surface) follow at the end.
 
 The grid has three different voxel edges (0.25, 0.125, 0.24) and three different counts, so a
 swapped axis or stride cannot pass; the slab's planes z = +-0.48 are voxel faces.
@@ -54,6 +56,8 @@ B_POOL_CAP = 1e-3
 # tolerance of 1e-6 per photon (1e-5 of the track), not a t test. In the stochastic voxels the
 # standard error is about ten times larger at 2e7 photons.
 B_TRACK_SLOP = 1e-6
+# (Scene D, whose surfaces are curved, derives its slop from the same rule leg by leg: see
+# D_EPS_SURFACE and d_slop() in the curved-surface section below.)
 # scene C
 C_IN = (6.0, 0.8, 0.7, 1.4)    # mus, mua, g, n of the slab
 C_OUT = (2.5, 0.4, 0.3, 1.0)
@@ -277,19 +281,22 @@ def check_batches(st):
 
 
 # ----------------------------------------------------------------- what a test asserts ----
-def evaluate_ab(which, jm, ab, ctr, n_batch, ref):
-    """Scenes A and B: a run in batches (run_batches) against ref = (T, p). ALPHA is shared by three
+def evaluate_ab(which, jm, ab, ctr, n_batch, ref, slop=None):
+    """Scenes A and B (and D, which names its own `slop` per photon and voxel and is held to B's
+    pooling rule): a run in batches (run_batches) against ref = (T, p). ALPHA is shared by three
     groups: the absorb counts (count_stats), the absorbed and escaped counters (one binomial: they
     sum to N) and the tracks (batch_stats). A voxel's track has at least N T_v / DIAG contributing
     photons, none of which leaves more than the voxel's diagonal: that is its event count."""
     t, p = ref
     n = n_batch * len(jm)
     a = ALPHA / 3.0
+    if slop is None:
+        slop = B_TRACK_SLOP if which == "b" else 0.0
     return {"which": which, "n": n,
             "counts": count_stats(ab.sum(axis=0), p, n, a),
             "z_absorbed": binomial_z(ctr["absorbed"], p.sum(), n),
             "z_escaped": binomial_z(ctr["escaped"], 1.0 - p.sum(), n), "z_bound": binomial_bound(a),
-            "tracks": batch_stats(jm, n_batch * t, n * t / DIAG, a, slop=n_batch * B_TRACK_SLOP if which == "b" else 0.0),
+            "tracks": batch_stats(jm, n_batch * t, n * t / DIAG, a, slop=n_batch * slop),
             "absorb_off_support": float(ab.sum(axis=0)[p == 0.0].sum()),
             "jmean_off_support": float(jm.sum(axis=0)[t == 0.0].sum()),
             "faults": ctr.get("faults", 0), "lost": n - ctr["absorbed"] - ctr["escaped"]}
@@ -891,3 +898,354 @@ def flat_mirror(st):
     for name, h in zip("xyz", st["halves"]):
         out[name + "_half_chi2"] = h["chi2"]
     return out
+
+
+# ------------------------------------------------------------------- curved surfaces (D) ----
+# A sphere of glass in vacuum against tests/analytic_ref.py (beam_legs, cast_sphere,
+# cast_triangles, centre_source_sphere; DESIGN.md §3.5 "Curved surfaces"). Shared by
+# tests/test_curved_analytic_cpu.py and tests/test_gpu_curved_analytic.py.
+#
+# The grid is grid() above, 8 x 12 x 10: the conditions below hold on it (34 voxels wholly inside
+# the sphere, 779 wholly outside, 147 cut). The sphere: centre D_CENTRE, off every voxel wall and
+# off the grid's centre, R = 0.55, n = 1.5, mus = 0, mua = D_MU (D_TIR_MU in D-tir), in vacuum
+# wider than the grid. Nothing scatters: every path is a tree of straight legs.
+#   D-centre  a point source at the sphere's centre (SDF forms): normal incidence everywhere
+#   D-beam    a pencil from outside, impact parameter 0.6 R, in no coordinate plane (SDF, mesh):
+#             15 legs with q >= 1e-14, 7 of them inside (rho a = 0.006 per bounce; mesh 17 and 8)
+#   D-tir     a pencil from inside at sin(incidence) = 0.8 > 1 / n (SDF, mesh): a star polygon of
+#             66 legs (mu chord = 0.495), none of which leaves the sphere; in the mesh form the
+#             facets' normals differ from the radial one and some hits transmit
+# Forms: "sdf" (sphere and vacuum box: ws_kernel, or transport_kernel with SMCRT_LEAN=0), "table"
+# (the same with nine index-matched vacuum spheres outside the grid, ten tops and more: the
+# cooperative EVAL with its table) and "mesh" (builders.icosphere(2, R, centre), a polyhedron
+# whose reference is cast_triangles on the same vertices and triangles). There is no voxel form:
+# a label volume has no curved surface.
+D_CENTRE = A_SRC
+D_R, D_N, D_MU, D_TIR_MU = 0.55, 1.5, 2.0, 0.75
+D_Q_MIN = 1e-14
+D_FORMS = ("sdf", "table", "mesh")
+D_MESH_LEVEL = 2
+D_BEAM_DIR = _unit((0.45, -0.3, -0.84))
+D_BEAM_B, D_BEAM_BACK = 0.33, 0.85      # the impact parameter (0.6 R) and the run back from the foot
+D_TIR_DIR = _unit((0.3, 0.7, -0.5))
+D_TIR_SIN, D_TIR_ALONG = 0.8, 0.1
+D_EXTRA_Y, D_EXTRA_Z, D_EXTRA_R = 0.95, -1.45, 0.04   # the table form's spheres: outside the grid
+D_CLEAR = 0.05
+# The track slop, derived from the engine's rule (tauint2) and not fitted: a photon stops within
+# 1e-8 of a surface, turns there, steps 2e-8 (+ 1e-8 per glancing round) past it along its ray, and
+# steps 1e-8 past every voxel wall. So a crossing is made at most D_EPS_SURFACE = 3e-8 off the
+# surface, which along a ray of cosine c to the normal is 3e-8 / c: the leg that arrives and the
+# leg that leaves are each off by that much in length where they end and start.
+# What a crossing made at radius R - e instead of R does to the later legs: reflection and
+# refraction about a radial normal keep Bouguer's invariant n |r x d| wherever on the ray they
+# happen, so no later impact parameter and no later angle of incidence changes. What changes is
+# the angle the path has turned through about the centre: a ray of impact parameter b spans
+# acos(b / r) from its closest approach to radius r, whose derivative by r is tan(theta) / r, so
+# the crossing turns every later leg about the centre by at most e (tan(theta_1) + tan(theta')) / R,
+# theta' the angle it leaves with (theta_1 reflected, theta_2 refracted). The turns add up along a
+# path, they do not compound. A leg after the crossings 1 .. m is therefore displaced by at most
+#   Delta = far * sum_j 3e-8 (tan(theta_1j) + tan(theta'_j)) / R,
+# far its largest distance from the centre. In a voxel a displacement Delta moves the leg's entry
+# through a wall normal to axis a by Delta / |d_a| along the ray and the wall's own step adds
+# 1e-8 / |d_a|, likewise for the exit through a wall normal to axis b; an end that lies on the
+# surface inside the voxel adds its 3e-8 / c instead; and a leg's track in a voxel is never off by
+# more than it is long there. Summed with the legs' q that is d_slop(), per photon and voxel; its
+# largest value over the voxels is the `slop` that batch_stats adds to the standard error of every
+# voxel of that case (d_track_slop). calcNormal's error on a sphere (h^2 / R^2 truncation, 1e-16 / h
+# cancellation: 1e-10 rad) is a thousandth of one crossing's turn and is covered by the margin
+# between 1e-8 + 2e-8 c and 3e-8. A mesh scene makes its crossing on the facet itself, without stop
+# or step, and a flat facet turns nothing: only the walls' 1e-8 remain. The sphere's
+# bound is applied to it unchanged, which is more than it needs.
+# Figures (d_conditions()): D-beam 3.8e-7 (SDF) and 1.1e-6 (mesh), D-tir 5.9e-7 and 9.4e-7 per
+# photon and voxel, beside B_TRACK_SLOP = 1e-6; in every voxel that holds at least
+# D_SLOP_MIN_TRACK of expected track per photon that is at most 4.9e-5 of the track, and the plain
+# sum of q x (3e-8 / c over the crossings before the leg) at most 6e-6 of it, which is held below
+# D_SLOP_SHARE (a less grazing beam otherwise). Below D_SLOP_MIN_TRACK a voxel holds a sliver of a
+# leg next to one of its edges, whose length any displacement changes by a large share of itself
+# whatever the beam's incidence; there the absolute bound is what is tested.
+D_EPS_SURFACE, D_EPS_WALL = 3e-8, 1e-8
+D_SLOP_SHARE = 1e-5   # of a voxel's expected track: the cap on q x (3e-8 / c) summed per voxel
+D_SLOP_MIN_TRACK = 1e-2
+
+
+def d_origin(case):
+    """The pencil's origin: off the centre by the impact parameter, across the beam."""
+    c = np.array(D_CENTRE)
+    if case == "beam":
+        d = np.array(D_BEAM_DIR)
+        u = np.cross(d, (0.3, 0.9, 0.2))
+        return tuple(c + D_BEAM_B * u / math.sqrt(float(u @ u)) - D_BEAM_BACK * d)
+    d = np.array(D_TIR_DIR)
+    u = np.cross(d, (0.8, -0.1, 0.6))
+    return tuple(c + D_TIR_SIN * D_R * u / math.sqrt(float(u @ u)) + D_TIR_ALONG * d)
+
+
+def d_mu(case):
+    return D_TIR_MU if case == "tir" else D_MU
+
+
+def d_extras():
+    """Centres of the table form's nine small spheres, all outside the grid."""
+    return [(-0.8 + 0.2 * i, D_EXTRA_Y, D_EXTRA_Z) for i in range(9)]
+
+
+def scene_d(case, form):
+    """(scene, source) of case "centre", "beam" or "tir" in `form`."""
+    glass, vac = scene.mono(0.0, d_mu(case), 0.0, D_N), scene.mono(0.0, 0.0, 0.0, 1.0)
+    if case == "centre":
+        assert form != "mesh", "D-centre has no mesh form: the polyhedron is not met at normal incidence"
+        src = scene.point_source(D_CENTRE)
+    else:
+        src = scene.pencil_source(d_origin(case), D_BEAM_DIR if case == "beam" else D_TIR_DIR)
+    if form == "mesh":
+        ms = scene.MeshScene([glass, vac], ambient=1)
+        return ms.add_surface(*builders.icosphere(D_MESH_LEVEL, D_R, D_CENTRE), 0, 1), src
+    tops = [scene.sphere(D_R, glass, 1, transform=scene.invert(scene.translate(D_CENTRE)))]
+    if form == "table":
+        tops += [scene.sphere(D_EXTRA_R, vac, i + 2, transform=scene.invert(scene.translate(p)))
+                 for i, p in enumerate(d_extras())]
+    return scene.Scene(tops + [scene.box((40.0, 40.0, 40.0), vac, len(tops) + 1)]), src
+
+
+D_CONTROLS = ("n+1%", "R+1%", "mu+1%", "s-polarised", "normal-tilted", "exit-normal-unturned",
+              "x-y-swapped", "x-z-swapped", "y-z-swapped")
+D_TILT, D_TILT_AXIS = 5e-3, (0.5, -0.6, 0.62)
+
+
+def _d_cast(form, radius=D_R):
+    if form == "mesh":
+        v, t = builders.icosphere(D_MESH_LEVEL, radius, D_CENTRE)
+        n = np.cross(v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]])
+        assert np.all((n * (v[t[:, 0]] - np.array(D_CENTRE))).sum(axis=1) > 0.0), "a facet wound inwards"
+        return AR.cast_triangles(v, t)
+    return AR.cast_sphere(D_CENTRE, radius)
+
+
+@functools.lru_cache(maxsize=None)
+def trace_d(case, form="sdf", control=None):
+    """beam_legs of D-beam or D-tir: (track, p_abs, legs, hits, paths). `control` names a reference
+    that is wrong on purpose (the negative controls only). The table form is the SDF form."""
+    form = "mesh" if form == "mesh" else "sdf"
+    n = 1.01 * D_N if control == "n+1%" else D_N
+    mu = (1.01 if control == "mu+1%" else 1.0) * d_mu(case)
+    cast = _d_cast(form, 1.01 * D_R if control == "R+1%" else D_R)
+    if control == "normal-tilted":
+        cast = AR.tilted(cast, D_TILT_AXIS, D_TILT)
+    out = AR.beam_legs(*faces(), d_origin(case), D_BEAM_DIR if case == "beam" else D_TIR_DIR, cast, n, 1.0, mu,
+                       D_Q_MIN, polarisation="s" if control == "s-polarised" else "unpolarised",
+                       exit_normal_unturned=control == "exit-normal-unturned")
+    if control is not None and control.endswith("-swapped"):
+        ax = control[0] + control[2]
+        out = (swapped(out[0], ax), swapped(out[1], ax)) + out[2:]
+    return out
+
+
+def reference_d(case, form="sdf", control=None):
+    """(T, p) of D-beam and D-tir: expected track and absorption probability per photon and voxel."""
+    return trace_d(case, form, control)[:2]
+
+
+def centre_d(control=None):
+    """centre_source_sphere of D-centre."""
+    return _centre_d(control)
+
+
+@functools.lru_cache(maxsize=None)
+def _centre_d(control):
+    return AR.centre_source_sphere(*faces(), D_CENTRE, 1.01 * D_R if control == "R+1%" else D_R,
+                                   1.01 * D_N if control == "n+1%" else D_N, (1.01 if control == "mu+1%" else 1.0) * D_MU)
+
+
+def reduce_centre(a, control=None):
+    """A grid [..., nz, ny, nx] of D-centre as [..., M + 1]: the voxels the surface does not cut,
+    then the sum of the cut ones. The -swapped controls exchange two axes of the data first."""
+    a = np.asarray(a, dtype=np.float64)
+    if control is not None and control.endswith("-swapped"):
+        flat = a.reshape(-1, NZ, NY, NX)
+        a = np.array([swapped(g, control[0] + control[2]) for g in flat]).reshape(a.shape)
+    cut = centre_d()["cut"]
+    return np.concatenate([a[..., ~cut], a[..., cut].sum(axis=-1, keepdims=True)], axis=-1)
+
+
+def reference_centre(control=None):
+    """(T, p) of D-centre in reduce_centre's layout. The cut mask is the right sphere's also under
+    a control, so that data and reference are pooled alike."""
+    control = None if control is None or control.endswith("-swapped") else control
+    ref = centre_d(control)
+    cut = centre_d()["cut"]
+    if control is None:
+        t = np.append(ref["track"][~cut], ref["cut_track"])
+        p = np.append(ref["p_abs"][~cut], ref["cut_p_abs"])
+    else:   # a wrong sphere cuts other voxels: what it leaves undetermined goes to the pooled bin by conservation
+        known = ~cut & ~ref["cut"]
+        t_all = ref["cut_track"] + float(ref["track"][~ref["cut"]].sum())
+        p_all = ref["cut_p_abs"] + float(ref["p_abs"][~ref["cut"]].sum())
+        t = np.append(np.where(known, ref["track"], 0.0)[~cut], 0.0)
+        p = np.append(np.where(known, ref["p_abs"], 0.0)[~cut], 0.0)
+        # the voxels the wrong sphere cuts but the right one does not: their share is unknown, and a
+        # control may not claim more than it knows, so they are given the right reference's values
+        gap = ~cut & ref["cut"]
+        good = centre_d()
+        t[:-1] += np.where(gap, good["track"], 0.0)[~cut]
+        p[:-1] += np.where(gap, good["p_abs"], 0.0)[~cut]
+        t[-1], p[-1] = t_all - t[:-1].sum(), p_all - p[:-1].sum()
+    return t, p
+
+
+def d_slop(case, form="sdf"):
+    """The bound on the systematic track error per photon of every voxel, (nz, ny, nx): see above."""
+    _, _, legs, _, paths = trace_d(case, form)
+    xe, ye, ze = faces()
+    zz, yy, xx = np.meshgrid(np.arange(NZ), np.arange(NY), np.arange(NX), indexing="ij")
+    lo = np.stack([xe[xx], ye[yy], ze[zz]], axis=-1)
+    hi = np.stack([xe[xx + 1], ye[yy + 1], ze[zz + 1]], axis=-1)
+    c = np.array(D_CENTRE)
+    out = np.zeros((NZ, NY, NX))
+
+    def tan(cosine):
+        return math.sqrt(max(0.0, 1.0 - cosine * cosine)) / cosine
+
+    for (o, d, q, length, _), path in zip(legs, paths):
+        end = o + length * d
+        far = max(math.sqrt(float((o - c) @ (o - c))), math.sqrt(float((end - c) @ (end - c))))
+        delta = far * sum(D_EPS_SURFACE * (tan(c1) + tan(c_out)) / D_R for c1, c_out in path)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ta, tb = (lo - o) / d, (hi - o) / d
+        t_in, t_out = np.minimum(ta, tb), np.maximum(ta, tb)
+        s0, s1 = t_in.max(axis=-1), t_out.min(axis=-1)
+        per_wall = (delta + D_EPS_WALL) / np.abs(d)
+        off_in = np.where(s0 > 0.0, per_wall[t_in.argmax(axis=-1)], D_EPS_SURFACE / path[-1][1] if path else 0.0)
+        on_surface = bool(np.all(np.abs(end) < np.array(HALF) - 1e-9))     # (the leg ends inside the grid)
+        c_end = abs(float(d @ (end - c))) / math.sqrt(float((end - c) @ (end - c)))
+        off_out = np.where(s1 < length, per_wall[t_out.argmin(axis=-1)], D_EPS_SURFACE / c_end if on_surface else 0.0)
+        run = np.minimum(s1, length) - np.maximum(s0, 0.0)
+        out += q * np.where(run > 1e-12, np.minimum(run, off_in + off_out), 0.0)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def d_track_slop(case, form="sdf"):
+    """The `slop` of evaluate_ab for a case: the largest d_slop() of a voxel."""
+    return float(d_slop(case, form).max())
+
+
+@functools.lru_cache(maxsize=None)
+def d_conditions(n=24 * 840_000):
+    """The conditions on scene D's inputs at n photons, asserted from the references alone; returns
+    the figures (tests/test_curved_analytic_cpu.py prints them): D-centre's voxel counts and fewest
+    events; per beam case and form the legs, hits, smallest incidence cosine, pooled shares, slop
+    and its shares of a voxel's track."""
+    xe, ye, ze = faces()
+    out = {}
+    assert np.all(np.abs(np.array(D_CENTRE)) + D_R < np.array(HALF)), "the sphere leaves the grid"
+    for a, e in enumerate((xe, ye, ze)):
+        assert np.min(np.abs(e - D_CENTRE[a])) > 1e-3 and abs(D_CENTRE[a]) > 1e-3
+    for p in d_extras():
+        assert any(abs(p[a]) - D_EXTRA_R > HALF[a] + D_CLEAR for a in range(3)), "an extra sphere near the grid"
+    c = centre_d()
+    t, p = reference_centre()
+    assert int(c["inside"].sum()) >= 30 and int(c["outside"].sum()) >= 300, (c["inside"].sum(), c["outside"].sum())
+    own_t, pool_t = _bins(n * t / DIAG)
+    own_p, pool_p = _bins(n * p)
+    assert pool_t is None and pool_p is None, "a D-centre voxel below MIN_EVENTS"
+    out["centre"] = {"inside": int(c["inside"].sum()), "outside": int(c["outside"].sum()), "cut": int(c["cut"].sum()),
+                     "min_track_events": float((n * t / DIAG).min()), "min_absorb_events": float((n * p[p > 0.0]).min())}
+    for case in ("beam", "tir"):
+        for form in ("sdf", "mesh"):
+            tr, pa, legs, hits, paths = trace_d(case, form)
+            for point, c1, q, inside, bary in hits:
+                for a, e in enumerate((xe, ye, ze)):
+                    assert np.min(np.abs(e - point[a])) > 1e-6, "a surface hit on a voxel wall"
+                if form == "mesh" and q >= 1e-9:
+                    assert bary > 1e-6, "a leg meets the edge of a facet"
+            for pooled, ref in ((_bins(n * pa)[1], pa), (_bins(n * tr / DIAG)[1], tr)):
+                share = 0.0 if pooled is None else float(ref.ravel()[pooled].sum() / ref.sum())
+                assert share <= B_POOL_CAP, (case, form, share)
+            slop = d_slop(case, form)
+            own = tr >= D_SLOP_MIN_TRACK
+            share = float((slop[own] / tr[own]).max())
+            shift = np.zeros_like(tr)   # sum of q x (3e-8 / c over the crossings before the leg), per voxel
+            for leg, path in zip(legs, paths):
+                shift += leg[2] * sum(D_EPS_SURFACE / min(pair) for pair in path) * (AR.leg_voxels(xe, ye, ze, leg) > 0.0)
+            shift_share = float((shift[own] / tr[own]).max())
+            assert shift_share <= D_SLOP_SHARE, (case, form, shift_share)
+            out[case, form] = {"legs": len(legs), "inside_legs": sum(1 for leg in legs if leg[4]), "hits": len(hits),
+                               "min_cos": min(h[1] for h in hits), "own_share_voxels": int(own.sum()), "slop": d_track_slop(case, form), "slop_share": share, "shift_share": shift_share,
+                               "p_abs": float(pa.sum()), "voxels": int(np.count_nonzero(tr))}
+    return out
+
+
+def evaluate_weighted(jm, ab, ctr, n_batch, ref, slop):
+    """A run of D-tir with FLAG_SURVIVAL_BIAS against ref = (T, p), by batch means as scene C's.
+    The sphere's albedo is 0, so a photon leaves its whole weight at its first interaction (absorb
+    holds fp64 weights that happen to be ones) and goes on with weight 0 if the roulette spares it:
+    what it then deposits is 0.0, wherever it goes, and how it ends (`absorbed`, `escaped`) follows
+    no law of the scene, so the counters are not tested. ALPHA is shared by the absorb grid and
+    the tracks, both batch_stats."""
+    t, p = ref
+    n = n_batch * len(jm)
+    a = ALPHA / 2.0
+    # (the reference follows no leg below D_Q_MIN: it misses at most D_Q_MIN / (1 - exp(-mu chord)) < 10 D_Q_MIN
+    # per photon, which is all that separates it from a batch whose every photon was absorbed)
+    return {"n": n, "counts": batch_stats(ab, n_batch * p, n * p, a, slop=n_batch * 10.0 * D_Q_MIN),
+            "tracks": batch_stats(jm, n_batch * t, n * t / DIAG, a, slop=n_batch * slop),
+            "absorb_off_support": float(ab.sum(axis=0)[p == 0.0].sum()), "absorb_sum": float(ab.sum()),
+            "jmean_off_support": float(jm.sum(axis=0)[t == 0.0].sum()), "faults": ctr.get("faults", 0)}
+
+
+def check_weighted(st):
+    assert st["faults"] == 0, st
+    assert st["absorb_off_support"] == 0.0 and st["jmean_off_support"] == 0.0, st
+    for group in ("counts", "tracks"):
+        assert st[group]["pooled_share"] < B_POOL_CAP, st[group]
+        check_batches(st[group])
+
+
+# D-beam's detectors, both forms: one circle across the first doubly refracted leg (outside, after
+# two crossings) and one across the first externally reflected leg (outside, after one), each
+# D_DET_RUN along the leg from the sphere, which is 0.3 or more from its surface. The bins are
+# rings D_DET_W wide; the disc is tilted against the leg and placed so that the leg lands in the
+# middle of ring D_DET_BIN = 1, at radius w. A ring sees only the radius, and a landing moved by
+# delta in the worst direction (through the disc's centre) leaves ring 1 once delta > 2.5 w: a
+# direction error of 1e-3 rad moves it by 4.2e-4 = 2.8 w, so it changes the bin whichever way it
+# points. (A landing far out in a wide disc would not notice an error along its ring.)
+D_DET_RUN, D_DET_W, D_DET_NBINS, D_DET_BIN = 0.42, 1.5e-4, 20, 1
+D_DET_TILT = (0.25, 0.1, -0.2)
+
+
+def _d_det_geometry(form):
+    _, _, legs, _, paths = trace_d("beam", form)
+    out = []
+    for crossings in (2, 1):
+        leg = next(lg for lg, path in zip(legs, paths) if len(path) == crossings and not lg[4]
+                   and (crossings == 1 or lg[2] > 0.1))
+        o, d = leg[0], leg[1]
+        at = o + D_DET_RUN * d
+        assert math.sqrt(float((at - np.array(D_CENTRE)) @ (at - np.array(D_CENTRE)))) - D_R >= 0.3 and leg[3] > D_DET_RUN + 0.01
+        n = d + np.array(D_DET_TILT)
+        n = n / math.sqrt(float(n @ n))
+        u = np.cross(n, d)
+        centre = at + D_DET_BIN * D_DET_W * u / math.sqrt(float(u @ u))
+        assert _disc_inside_grid(centre, n, D_DET_W * D_DET_NBINS)
+        out.append((tuple(centre), tuple(n), D_DET_W * D_DET_NBINS, D_DET_NBINS))
+    return out
+
+
+def dets_d(form):
+    return [scene.circle_dect(c, n, 1, radius, nb) for c, n, radius, nb in _d_det_geometry(form)]
+
+
+@functools.lru_cache(maxsize=None)
+def expected_d(form, control=None):
+    """(p per detector, landings per detector) of dets_d(form); the discs stay where the right
+    reference puts them under a control."""
+    legs = trace_d("beam", form, control)[2]
+    mu = (1.01 if control == "mu+1%" else 1.0) * D_MU
+    ps, lands = [], []
+    for c, n, radius, nb in _d_det_geometry(form):
+        p, landed = AR.legs_on_disc(legs, mu, c, n, AR.circle_edges(radius, nb))
+        ps.append(p)
+        lands.append(landed)
+    if control is None:
+        assert [[b for b, _, _, _ in ld] for ld in lands] == [[D_DET_BIN], [D_DET_BIN]], lands
+    return ps, lands

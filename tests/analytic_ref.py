@@ -7,6 +7,10 @@ Grids are given by their three arrays of voxel faces (`faces(n, half)`), results
   point_source_track   scene A: an isotropic point source in a homogeneous absorber
   point_source_escape  scene A: the probability of leaving the grid unabsorbed
   beam_slab            scene B: a pencil beam through an index-mismatched absorbing slab
+  beam_legs            scene D: the same beam against any surface given as a ray cast
+  cast_sphere, cast_triangles   scene D: the casts of a sphere and of a closed triangle surface
+  sphere_beam_series   scene D: the geometric series of a beam's legs inside a sphere
+  centre_source_sphere scene D: a point source at the centre of an absorbing glass sphere
 
 and per-bin expectations of the detectors (their hit rules are stated above circle_edges):
 
@@ -54,6 +58,8 @@ def _gl(order=GL_ORDER):
 # singular point. The integrand is smooth on a face; a voxel face is one Gauss-Legendre panel.
 
 def _phi(rho, mu):
+    if mu == 0.0:
+        return rho / (4.0 * math.pi)
     return -np.expm1(-mu * rho) / (4.0 * math.pi * mu)
 
 
@@ -86,9 +92,10 @@ def _face_terms(xe, ye, ze, src, f, order):
 def point_source_track(xe, ye, ze, src, mu, order=GL_ORDER) -> np.ndarray:
     """T(V) of every voxel of the grid with faces xe, ye, ze: the expected track length per photon
     of an isotropic point source at `src` (on no face) in a homogeneous medium with mus = 0 and
-    mua = mu > 0. The probability of absorption in V is mu * T(V)."""
+    mua = mu. The probability of absorption in V is mu * T(V). mu = 0 gives the integral of
+    1 / (4 pi r^2) and mu < 0 that of exp(|mu| r) / (4 pi r^2) (a stream that runs towards the
+    source, scene D): Phi is the same radial integral for either sign."""
     mu = float(mu)
-    assert mu > 0.0
     for e, s in zip((xe, ye, ze), src):
         assert np.min(np.abs(np.asarray(e) - s)) > 0.0, "the source lies on a voxel face"
     jx, jy, jz = _face_terms(xe, ye, ze, src, lambda r: _phi(r, mu), order)
@@ -256,6 +263,233 @@ def beam_slab_legs(xe, ye, ze, origin, direction, z_half, n_in, n_out=1.0, mu_in
             eta = n1 / n2
             todo.append((p, np.array([eta * d[0], eta * d[1], math.copysign(cos2, d[2])]), q * (1.0 - r), not inside))
     return out
+
+
+# ---------------------------------------------------------------------------- scene D ----
+# Curved surfaces. Nothing scatters, so a photon's path is a tree of straight legs with Fresnel
+# probabilities at the nodes; the surface enters only as a ray cast, `cast(o, d)` -> None or
+# (s, N[, b]): the distance s > 0 to the next surface point along the unit vector d, the unit
+# normal N there pointing out of the body, and for a triangle surface the smallest barycentric
+# coordinate b of the hit in its facet.
+CAST_EPS = 1e-9   # a leg that starts on the surface does not meet it again at its own origin
+
+
+def cast_sphere(centre, radius):
+    """The cast of the sphere |x - centre| = radius: the roots of s^2 + 2 (oc . d) s + |oc|^2 - R^2
+    and the radial normal."""
+    c, r = np.asarray(centre, dtype=np.float64), float(radius)
+
+    def cast(o, d):
+        oc = o - c
+        b = float(oc @ d)
+        disc = b * b - (float(oc @ oc) - r * r)
+        if disc <= 0.0:
+            return None
+        root = math.sqrt(disc)
+        for s in (-b - root, -b + root):
+            if s > CAST_EPS:
+                p = oc + s * d
+                return s, p / math.sqrt(float(p @ p))
+        return None
+    return cast
+
+
+def cast_triangles(verts, tris):
+    """The cast of a closed surface of triangles wound anticlockwise seen from outside: every
+    triangle is tried (Moeller-Trumbore: the ray's point o + s d written as v0 + u e1 + v e2 by
+    Cramer's rule), the nearest hit wins, the normal is e1 x e2 of that facet."""
+    verts = np.asarray(verts, dtype=np.float64)
+    tris = np.asarray(tris, dtype=np.int64)
+    v0 = verts[tris[:, 0]]
+    e1, e2 = verts[tris[:, 1]] - v0, verts[tris[:, 2]] - v0
+    nrm = np.cross(e1, e2)
+    nrm = nrm / np.sqrt((nrm * nrm).sum(axis=1))[:, None]
+
+    def cast(o, d):
+        pv = np.cross(d[None, :], e2)
+        det = (e1 * pv).sum(axis=1)
+        ok = det != 0.0
+        inv = 1.0 / np.where(ok, det, 1.0)
+        tv = o[None, :] - v0
+        u = (tv * pv).sum(axis=1) * inv
+        qv = np.cross(tv, e1)
+        v = (qv * d[None, :]).sum(axis=1) * inv
+        s = (e2 * qv).sum(axis=1) * inv
+        bary = np.minimum(np.minimum(u, v), 1.0 - u - v)
+        hit = ok & (bary >= 0.0) & (s > CAST_EPS)
+        if not hit.any():
+            return None
+        i = int(np.argmin(np.where(hit, s, np.inf)))
+        return float(s[i]), nrm[i], float(bary[i])
+    return cast
+
+
+def tilted(cast, axis, angle):
+    """`cast` with every normal turned by `angle` about `axis` (Rodrigues). A negative control."""
+    k = np.asarray(axis, dtype=np.float64)
+    k = k / math.sqrt(float(k @ k))
+
+    def wrapped(o, d):
+        hit = cast(o, d)
+        if hit is None:
+            return None
+        n = hit[1]
+        n = n * math.cos(angle) + np.cross(k, n) * math.sin(angle) + k * float(k @ n) * (1.0 - math.cos(angle))
+        return (hit[0], n) + tuple(hit[2:])
+    return wrapped
+
+
+def beam_legs(xe, ye, ze, origin, direction, cast, n_in, n_out, mu_in, q_min, polarisation="unpolarised",
+              exit_normal_unturned=False):
+    """beam_slab for any body: a pencil beam from `origin` (inside the grid, which ends the world)
+    along `direction` against the body whose surface is `cast` (index n_in, mua = mu_in, mus = 0;
+    around it index n_out, no absorption). At a hit with outward normal N and incidence cosine
+    c1 = |d . N| the reflected leg is d - 2 (d . N) N and the refracted one
+    eta d + (eta c1 - c2) m, eta = n1 / n2, m the normal turned against the ray. Every leg that
+    carries q >= q_min is followed. Returns (track, p_abs, legs, hits, paths): the grids of
+    beam_slab, the legs in the format of beam_slab_legs, per followed surface hit
+    (point, c1, q on arrival, from inside?, barycentric minimum or None), and per leg the tuple of
+    the crossings before it, in order, each as (c1, the cosine the path left the surface with:
+    c1 reflected, c2 refracted).
+    exit_normal_unturned (a negative control) refracts an outgoing ray about N as it stands."""
+    xe, ye, ze = (np.asarray(e, dtype=np.float64) for e in (xe, ye, ze))
+    zz, yy, xx = np.meshgrid(np.arange(len(ze) - 1), np.arange(len(ye) - 1), np.arange(len(xe) - 1), indexing="ij")
+    lo = np.stack([xe[xx], ye[yy], ze[zz]], axis=-1)
+    hi = np.stack([xe[xx + 1], ye[yy + 1], ze[zz + 1]], axis=-1)
+    glo = np.array([xe[0], ye[0], ze[0]])
+    ghi = np.array([xe[-1], ye[-1], ze[-1]])
+    track = np.zeros(lo.shape[:-1])
+    p_abs = np.zeros(lo.shape[:-1])
+    d0 = np.asarray(direction, dtype=np.float64)
+    d0 = d0 / math.sqrt(float(d0 @ d0))
+    o0 = np.asarray(origin, dtype=np.float64)
+    assert np.all(o0 > glo) and np.all(o0 < ghi)
+    first = cast(o0, d0)
+    todo = [(o0, d0, 1.0, first is not None and float(first[1] @ d0) > 0.0, ())]  # leaving first: it starts inside
+    legs, hits, paths = [], [], []
+    while todo:
+        o, d, q, inside, path = todo.pop()
+        mu = mu_in if inside else 0.0
+        _, s_exit = _clip(glo, ghi, o, d, math.inf)
+        s_exit = float(s_exit)
+        hit = cast(o, d)
+        s_hit = math.inf if hit is None else hit[0]
+        s_end = min(s_exit, s_hit)
+        legs.append((o, d, q, s_end, inside))
+        paths.append(path)
+        s0, s1 = _clip(lo, hi, o, d, s_end)
+        on = s1 - s0 > 1e-12
+        if mu > 0.0:
+            w = np.where(on, np.exp(-mu * np.where(on, s0, 0.0)) - np.exp(-mu * np.where(on, s1, 0.0)), 0.0)
+            track += q * w / mu
+            p_abs += q * w
+        else:
+            track += q * np.where(on, s1 - s0, 0.0)
+        if s_hit >= s_exit:
+            continue
+        q = q * math.exp(-mu * s_hit)
+        if q < q_min:
+            continue
+        p = o + s_hit * d
+        nrm = hit[1]
+        dn = float(d @ nrm)
+        assert (dn > 0.0) == inside, "the surface is met from the wrong side"
+        n1, n2 = (n_in, n_out) if inside else (n_out, n_in)
+        c1 = abs(dn)
+        r, c2 = fresnel_unpolarised(c1, n1, n2, polarisation)
+        hits.append((p, c1, q, inside, hit[2] if len(hit) > 2 else None))
+        if q * r >= q_min:
+            todo.append((p, d - 2.0 * dn * nrm, q * r, inside, path + ((c1, c1),)))
+        if c2 is not None and q * (1.0 - r) >= q_min:
+            eta = n1 / n2
+            m = nrm if (dn < 0.0 or exit_normal_unturned) else -nrm
+            t = eta * d + (eta * c1 - c2) * m
+            todo.append((p, t / math.sqrt(float(t @ t)), q * (1.0 - r), not inside, path + ((c1, c2),)))
+    return track, p_abs, legs, hits, paths
+
+
+def leg_voxels(xe, ye, ze, leg):
+    """The length of one leg (o, d, q, length, inside) in every voxel, (nz, ny, nx)."""
+    xe, ye, ze = (np.asarray(e, dtype=np.float64) for e in (xe, ye, ze))
+    zz, yy, xx = np.meshgrid(np.arange(len(ze) - 1), np.arange(len(ye) - 1), np.arange(len(xe) - 1), indexing="ij")
+    lo = np.stack([xe[xx], ye[yy], ze[zz]], axis=-1)
+    hi = np.stack([xe[xx + 1], ye[yy + 1], ze[zz + 1]], axis=-1)
+    s0, s1 = _clip(lo, hi, leg[0], leg[1], leg[3])
+    return np.where(s1 - s0 > 1e-12, s1 - s0, 0.0)
+
+
+def ball_voxels(xe, ye, ze, centre, radius):
+    """(inside, outside): the voxels wholly inside and wholly outside the ball, (nz, ny, nx), by
+    the farthest and the nearest point of each voxel from the centre."""
+    near2, far2 = 0.0, 0.0
+    for e, s, shape in ((xe, centre[0], (1, 1, -1)), (ye, centre[1], (1, -1, 1)), (ze, centre[2], (-1, 1, 1))):
+        e = np.asarray(e, dtype=np.float64)
+        a, b = e[:-1] - s, e[1:] - s
+        near = np.where((a < 0.0) & (b > 0.0), 0.0, np.minimum(np.abs(a), np.abs(b)))
+        near2 = near2 + (near ** 2).reshape(shape)
+        far2 = far2 + (np.maximum(np.abs(a), np.abs(b)) ** 2).reshape(shape)
+    return far2 < radius * radius, near2 > radius * radius
+
+
+def sphere_beam_series(sin_i, radius, n, mu, from_inside=False, first_run=0.0):
+    """The legs of a beam in a sphere of index n and mua = mu in vacuum, in closed form. A ray that
+    meets a sphere at the incidence angle i keeps it at every later hit, so every interior chord is
+    c = 2 R cos t (t the angle inside) and every hit has one reflectance rho.
+    From outside (sin_i = impact parameter / R): interior leg k starts with q_k = (1 - rho) (rho a)^k,
+    a = exp(-mu c). From inside (sin_i the sine inside, first_run the run to the first hit):
+    q_0 = 1 and q_k = exp(-mu first_run) rho^k a^(k-1).
+    Returns a dict: rho, chord, absorbed, escaped, reflected (the share that never enters) and
+    q(k)."""
+    if from_inside:
+        cos_t = math.sqrt(1.0 - sin_i * sin_i)
+        rho, _ = fresnel_unpolarised(cos_t, n, 1.0)
+        chord = 2.0 * radius * cos_t
+        a, a0 = math.exp(-mu * chord), math.exp(-mu * first_run)
+        escaped = a0 * (1.0 - rho) / (1.0 - rho * a) if rho * a < 1.0 else 0.0
+        return {"rho": rho, "chord": chord, "escaped": escaped, "absorbed": 1.0 - escaped, "reflected": 0.0,
+                "q": lambda k: 1.0 if k == 0 else a0 * rho ** k * a ** (k - 1)}
+    rho, cos_t = fresnel_unpolarised(math.sqrt(1.0 - sin_i * sin_i), 1.0, n)
+    back, _ = fresnel_unpolarised(cos_t, n, 1.0)
+    assert abs(back - rho) < 1e-14   # (Stokes: the same reflectance from either side)
+    chord = 2.0 * radius * cos_t
+    a = math.exp(-mu * chord)
+    absorbed = (1.0 - rho) * (1.0 - a) / (1.0 - rho * a)
+    return {"rho": rho, "chord": chord, "absorbed": absorbed, "escaped": rho + (1.0 - rho) ** 2 * a / (1.0 - rho * a),
+            "reflected": rho, "q": lambda k: (1.0 - rho) * (rho * a) ** k}
+
+
+def centre_source_sphere(xe, ye, ze, centre, radius, n, mu, order=GL_ORDER):
+    """An isotropic point source at the centre of a sphere (index n, mua = mu > 0, mus = 0) in
+    vacuum: every ray meets the surface at normal incidence, reflects with r0 = ((n - 1) / (n + 1))^2
+    and runs back along its diameter, through the centre and on to the opposite side. With
+    D = 1 - r0 exp(-2 mu R) the expected track density per photon is g(r) / (4 pi r^2),
+      inside   g = [exp(-mu r) + r0 exp(-mu (2 R - r))] / D   (the streams away from and towards the centre),
+      outside  g = (1 - r0) exp(-mu R) / D = P(escape the sphere),
+    so a voxel wholly inside holds [T(mu) + r0 exp(-2 mu R) T(-mu)] / D and one wholly outside
+    g T(0), T = point_source_track. The voxels the surface cuts are given as one pooled sum, exact
+    by conservation: the interior track is P(absorbed) / mu in all, the exterior track inside the
+    grid g (sum of T(0) over the grid - R), R being the integral of 1 / (4 pi r^2) over the ball.
+    Returns a dict: track, p_abs (the cut voxels hold NaN), inside, outside, cut (masks),
+    cut_track, cut_p_abs, p_escape (from the sphere; no photon is absorbed outside)."""
+    xe, ye, ze = (np.asarray(e, dtype=np.float64) for e in (xe, ye, ze))
+    c, r, mu = np.asarray(centre, dtype=np.float64), float(radius), float(mu)
+    assert mu > 0.0
+    r0 = ((n - 1.0) / (n + 1.0)) ** 2
+    dd = 1.0 - r0 * math.exp(-2.0 * mu * r)
+    g_out = (1.0 - r0) * math.exp(-mu * r) / dd
+    inside, outside = ball_voxels(xe, ye, ze, c, r)
+    cut = ~(inside | outside)
+    t_out = point_source_track(xe, ye, ze, c, mu, order)
+    t_in = point_source_track(xe, ye, ze, c, -mu, order)
+    t_0 = point_source_track(xe, ye, ze, c, 0.0, order)
+    track = np.where(inside, (t_out + r0 * math.exp(-2.0 * mu * r) * t_in) / dd, g_out * t_0)
+    p_abs = np.where(inside, mu * track, 0.0)
+    p_absorbed = 1.0 - g_out
+    cut_track = p_absorbed / mu + g_out * (float(t_0.sum()) - r) - float(track[~cut].sum())
+    cut_p_abs = p_absorbed - float(p_abs[inside].sum())
+    track[cut], p_abs[cut] = np.nan, np.nan
+    return {"track": track, "p_abs": p_abs, "inside": inside, "outside": outside, "cut": cut,
+            "cut_track": cut_track, "cut_p_abs": cut_p_abs, "p_escape": g_out, "r0": r0}
 
 
 # --------------------------------------------------------------------------- detectors ----
