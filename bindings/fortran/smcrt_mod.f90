@@ -302,6 +302,13 @@ module smcrt_mod
             integer(c_int64_t), intent(out) :: n
         end function smcrt_scene_invoxel_segments
 
+        integer(c_int) function smcrt_scene_out_of_order_handouts(scene, n) &
+                bind(C, name="smcrt_scene_out_of_order_handouts")
+            import :: c_int, c_int64_t, c_ptr
+            type(c_ptr), value           :: scene
+            integer(c_int64_t), intent(out) :: n
+        end function smcrt_scene_out_of_order_handouts
+
         integer(c_int) function smcrt_spectral_sample(sp, mode, seed, draw, out) &
                 bind(C, name="smcrt_spectral_sample")
             import :: c_int, c_int32_t, c_int64_t, smcrt_spectral, smcrt_optprops

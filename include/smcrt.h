@@ -876,6 +876,13 @@ int smcrt_scene_deposit_regime(const smcrt_scene* scene, int32_t* regime);
  * (jmean up to the order of its fp64 sums). */
 int smcrt_scene_invoxel_segments(smcrt_scene* scene, int64_t* out);
 
+/* The segments of this scene's finished lean launches that a photon handed to a walker wave in a
+ * slot other than the one a fixed rotation over its slots would have taken (the photon takes
+ * any free slot: segments finish out of order), a running total since the scene
+ * was created, counted like smcrt_scene_invoxel_segments. A schedule statistic: it varies from
+ * run to run and no tally depends on it. */
+int smcrt_scene_out_of_order_handouts(smcrt_scene* scene, int64_t* out);
+
 /* Normalisation of writer.f90:25-52 (normalise_fluence): grid *= nx*ny*nz / nphotons,
  * i.e. (8*xmax*ymax*zmax)/(nphotons*dx*dy*dz). Host-side helper on an fp32 grid. */
 int smcrt_normalise_fluence(float* grid, const smcrt_grid* g, uint64_t nphotons);

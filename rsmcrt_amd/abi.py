@@ -309,7 +309,7 @@ EXPORTED_SYMBOLS = [
     "smcrt_multi_scene", "smcrt_multi_run", "smcrt_multi_accumulate", "smcrt_multi_collect",
     "smcrt_multi_device_photons", "smcrt_multi_destroy", "smcrt_job_run_devices",
     "smcrt_spectral_sample", "smcrt_scene_set_spectral", "smcrt_scene_check",
-    "smcrt_scene_invoxel_segments",
+    "smcrt_scene_invoxel_segments", "smcrt_scene_out_of_order_handouts",
     "smcrt_scene_set_path_tracking", "smcrt_scene_path_counts", "smcrt_scene_read_paths", "smcrt_write_paths",
     "smcrt_job_history_filename",
     "smcrt_scene_set_phasor", "smcrt_scene_read_phasor", "smcrt_scene_reset_phasor",

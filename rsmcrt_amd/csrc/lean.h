@@ -33,7 +33,8 @@
 //     its tflag, error flags and cells when a walker finishes it.
 //   * The final cells of a deferred segment land in the photon's slot (pcell); a photon that
 //     must record an absorption (or its record) waits until its segments are done and reads
-//     them. Its RNG draw is taken back first, so the draw sequence is unchanged.
+//     those of the slot it pushed last (the slots are taken in no fixed order, ws.h). Its RNG
+//     draw is taken back first, so the draw sequence is unchanged.
 //
 // Why a deferred segment cannot leave the grid: dda_step moves each coordinate either by
 // dir_a * dcell (exact up to rounding) or, on the crossing axis, to face +- delta (1e-8,
@@ -109,7 +110,7 @@ struct LeanPhoton {
   double tau, taurun, d, minabs;
   int32_t layer;
   int32_t xcell, ycell, zcell;  // valid with LF_CELLS
-  uint32_t hop, loopc, st, seq;  // seq: the slot of the next segment
+  uint32_t hop, loopc, st, seq;  // seq: the slot of the last segment handed out | an event's free slot << 2 (ws.h)
   uint32_t f;                    // LF_* flags
   __device__ __forceinline__ bool has(uint32_t b) const { return (f & b) != 0; }
   __device__ __forceinline__ void set(uint32_t b) { f |= b; }

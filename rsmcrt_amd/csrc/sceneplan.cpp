@@ -64,6 +64,8 @@ LaunchKnobs read_launch_knobs() {
   if (const char* cd = std::getenv("SMCRT_DEBUG_CLAIM_DELAY")) k.claim_delay = (uint32_t)std::strtoul(cd, nullptr, 10);
   const char* de = std::getenv("SMCRT_DEBUG_DROP_EVENT");
   k.drop_event = de && de[0] == '1';
+  const char* el = std::getenv("SMCRT_DEBUG_EVAL_LOOP");
+  k.eval_loop = el && el[0] == '1';
   if (const char* pv = std::getenv("SMCRT_PATH_VERTICES")) k.path_vertices = (int32_t)std::strtol(pv, nullptr, 10);
   if (const char* pm = std::getenv("SMCRT_PATH_MAX")) k.path_max = (int64_t)std::strtoll(pm, nullptr, 10);
   return k;

@@ -39,6 +39,7 @@ enum QueueWord : int {
   Q_LEAN_HAZARDS,        // deferred lean segments that ended in tflag or an error stop (lean.h)
   Q_WATCHDOG,            // the first expired wait: site | (block + 1) << 8
   Q_INVOXEL,             // segments deposited by ws_kernel's photon waves (invoxel.h)
+  Q_OOO_HANDOUTS,        // ws_kernel hand-outs into a slot other than the next in rotation (ws.h)
   Q_COUNT
 };
 constexpr int N_QUEUES = Q_CALLER + 1;  // launch streams: each has a queue head, a KCold ring, a lane scratch
@@ -79,6 +80,7 @@ struct LaunchKnobs {  // read_launch_knobs(): at every launch
   double watchdog_ms = DEFAULT_WATCHDOG_MS;  // SMCRT_WATCHDOG_MS; 0: unbounded waits
   uint32_t claim_delay = 0;  // SMCRT_DEBUG_CLAIM_DELAY (tests only)
   bool drop_event = false;   // SMCRT_DEBUG_DROP_EVENT=1 (tests only: the watchdog's proof)
+  bool eval_loop = false;    // SMCRT_DEBUG_EVAL_LOOP=1 (tests only: ws_kernel's EVAL takes no pairs)
   bool diag_done = false;    // SMCRT_DIAG_DONE=1 (diagnostic builds: completion times)
 };
 struct PoolKnobs {  // read_pool_knobs(): when the record pool is (re)allocated

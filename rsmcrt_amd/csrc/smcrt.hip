@@ -801,10 +801,12 @@ static int diag_report(hipStream_t stream, bool lean) {
     std::fprintf(stderr, "[diag-ws] walker iters %llu: idle %.3f, busy lanes/iter %.1f, pending lanes/iter %.1f | "
                  "photon trips %llu: sleep %.3f, idle lanes %.1f, sync-waiting %.2f, slot-blocked %.2f, EVAL lanes "
                  "%.1f, pushes %.2f, P7 runs %.3f (lanes/run %.1f), event-waiting %.2f | producer waits %llu | event "
-                 "iters %llu, lanes/iter %.1f | emissions waiting for a slot %llu lane-trips\n",
+                 "iters %llu, lanes/iter %.1f | emissions waiting for a slot %llu lane-trips | out-of-order hand-outs "
+                 "%llu (%.3f of the pushes)\n",
                  h[20], h[21] / wi, h[22] / wi, h[23] / wi, h[24], h[25] / pt, h[30] / pt, h[27] / pt, h[26] / pt,
                  h[31] / pt, h[32] / pt, h[28] / pt, (double)h[29] / (double)std::max(1ull, h[28]), h[36] / pt, h[33],
-                 h[34], (double)h[35] / (double)std::max(1ull, h[34]), h[51]);
+                 h[34], (double)h[35] / (double)std::max(1ull, h[34]), h[51], h[52],
+                 (double)h[52] / (double)std::max(1ull, h[32]));
     // region times (ws.h WST): shares of each role's wave time
     const char* np[8] = {"fetch", "poll", "eval", "p3p4", "handout", "p5p6", "p7", "p8"};
     double tp = 0, tw = 0, te = 0;
@@ -905,6 +907,7 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.far_steps = s->d_queue + Q_FAR_STEPS;
   Ch.lean_hazards = s->d_queue + Q_LEAN_HAZARDS;
   Ch.invoxel_segs = s->d_queue + Q_INVOXEL;
+  Ch.ooo_handouts = s->d_queue + Q_OOO_HANDOUTS;
   Ch.lane_scratch = nullptr;  // (per launch stream: enqueue_transport)
   Ch.watchdog = watchdog_word(s);
   const bool hist = run.hist, phas = run.phas, scr = run.scr;  // (the run's launch choice)
@@ -972,7 +975,7 @@ static int fill_params(smcrt_scene* s, const smcrt_source* src, const smcrt_run_
   Ch.watchdog_ticks = knobs.watchdog_ms > 0.0 ? (uint64_t)(knobs.watchdog_ms * (double)s->wall_khz) : 0ull;
   K.rec_pool = nullptr; K.n_chunks = 0; K.hist_tiles = 0; K.bucket_tiles = 0; K.n_buckets = 0;
   K.claim_delay = knobs.claim_delay;
-  K.lean_debug = s->lean_debug | (knobs.drop_event ? 4u : 0u);
+  K.lean_debug = s->lean_debug | (knobs.drop_event ? 4u : 0u) | (knobs.eval_loop ? 8u : 0u);
   K.ws_invoxel = ws_invoxel_on(s->ws_invoxel, plan_xf(*s)) ? 1u : 0u;  // (read by ws_kernel only)
   lean_margins(K.lean_debug, s->grid, K.lean_lo, K.lean_hi);
   return SMCRT_OK;
@@ -1416,6 +1419,17 @@ int smcrt_scene_invoxel_segments(smcrt_scene* s, int64_t* out) {
   HIPCHK(hipSetDevice(s->device));
   unsigned long long n = 0;  // (a running total: segments of launches still running count later)
   HIPCHK(hipMemcpy(&n, s->d_queue + Q_INVOXEL, sizeof(n), hipMemcpyDeviceToHost));
+  *out = (int64_t)n;
+  return SMCRT_OK;
+}
+
+int smcrt_scene_out_of_order_handouts(smcrt_scene* s, int64_t* out) {
+  if (!s || !out) return fail(SMCRT_ERR_INVALID_ARG, "NULL argument");
+  if (const int vst = smcrt::scene_needs_sdf(s, "smcrt_scene_out_of_order_handouts")) return vst;
+  std::lock_guard<std::mutex> g(s->mu);
+  HIPCHK(hipSetDevice(s->device));
+  unsigned long long n = 0;  // (a running total: hand-outs of launches still running count later)
+  HIPCHK(hipMemcpy(&n, s->d_queue + Q_OOO_HANDOUTS, sizeof(n), hipMemcpyDeviceToHost));
   *out = (int64_t)n;
   return SMCRT_OK;
 }

@@ -81,6 +81,7 @@ struct KCold {
   unsigned long long* far_steps;  // march steps taken by the far-field march (far.h), running total
   unsigned long long* lean_hazards;  // deferred lean segments ending in tflag / a fault (lean.h), running total
   unsigned long long* invoxel_segs;  // segments deposited by ws_kernel's photon waves (invoxel.h), running total
+  unsigned long long* ooo_handouts;  // ws_kernel hand-outs into a slot other than the next in rotation (ws.h), running total
   double* lane_scratch;       // ws_kernel's per-photon-lane Fresnel/detector state (ws.h WX_*), or null
   // the watchdog (round 6): every cross-wave wait of the kernels is bounded by watchdog_ticks of
   // s_memrealtime (SMCRT_WATCHDOG_MS; 0 = unbounded); the first wait past it stores
@@ -198,7 +199,9 @@ struct KParams {
   // debug knob (SMCRT_DEBUG_LEAN_MARGIN, tests only), bits 0-1: 0 = lean.h's margin; 1 = no
   // margin; 2 = every segment that starts in the grid is deferred, so escapes become counted
   // hazards. Bit 2 (SMCRT_DEBUG_DROP_EVENT, tests only): photon lane 0 of block 0 marks its first
-  // event queued without queueing it (the hang class the watchdog turns into a counted fault)
+  // event queued without queueing it (the hang class the watchdog turns into a counted fault).
+  // Bit 3 (SMCRT_DEBUG_EVAL_LOOP, tests only): the photon waves of a ws_kernel whose EVAL takes
+  // pairs (ws.h WsTraits) evaluate one top at a time, as the other instantiations do
   uint32_t lean_debug;
   // SMCRT_WS_INVOXEL (sceneplan.h ws_invoxel_on): ws_kernel's photon waves deposit the segments that end inside
   // their start voxel themselves (invoxel.h) instead of handing them to a walker
@@ -1083,12 +1086,13 @@ struct EvalOut {
 // NEST: the program may hold nested-model ops (PROG_SUB); only the general instantiation
 // evaluates such scenes (smcrt.hip), so every other caller compiles without them.
 // PAIRS: two consecutive top-level spheres or boxes at a time (see below); transport_kernel
-// (M5 46.3-47.6 vs 43.4-43.8 M photons/s) but not ws_kernel's photon waves (M1 -1.4 %, M0
-// -2.3 %), profiles/r06_s6/ab_eval_pairs.txt
+// (M5 46.3-47.6 vs 43.4-43.8 M photons/s, profiles/r06_s6/ab_eval_pairs.txt) and the ws_kernel
+// instantiations that ws.h WsTraits names; pairs_on = false (a tests-only knob of ws_kernel)
+// takes the tops one by one in a PAIRS instantiation
 template <bool NEST = false, bool PAIRS = false>
 __device__ __forceinline__ EvalOut eval_sdfs(const smcrt_sdf_node* __restrict__ nodes,
                                              const ProgOp* __restrict__ prog, int32_t n_prog, V3 q,
-                                             bool mask_le, int32_t capi, int32_t capj) {
+                                             bool mask_le, int32_t capi, int32_t capj, bool pairs_on = true) {
   EvalOut r;
   r.minabs = __builtin_inf();
   r.minv = __builtin_inf();
@@ -1102,7 +1106,7 @@ __device__ __forceinline__ EvalOut eval_sdfs(const smcrt_sdf_node* __restrict__ 
     // two consecutive top-level spheres or boxes (any order) as straight-line code: the kinds
     // are constants there (sdf_prim_s: the same operations), so the two evaluations' latency
     // chains overlap; folded in program order, as below (wave-uniform branch)
-    if (PAIRS && !NEST && ip + 1 < n_prog && op.action == PROG_TOP && op.top > 0) {
+    if (PAIRS && !NEST && pairs_on && ip + 1 < n_prog && op.action == PROG_TOP && op.top > 0) {
       const ProgOp op2 = prog[ip + 1];
       if (op2.action == PROG_TOP && op2.top > 0) {
         const smcrt_sdf_node* n1 = nodes + __builtin_amdgcn_readfirstlane(op.node);

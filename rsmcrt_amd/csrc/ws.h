@@ -37,6 +37,24 @@
 // Segments and the block ring. A photon's segment lives in one of its WS_SLOTS slots (`seg`,
 // structure of arrays over the photon lanes), which its busy bit guards: the photon writes a
 // slot only while the bit is clear and sets it, the walker clears it when the walk is done. The
+// photon takes any free slot, the lowest clear bit of its busy word (ws_pick): segments are 2 to
+// more than 30 crossings long and finish out of order, so a fixed rotation blocked a photon on
+// one busy slot while another was free. What holds for the slots:
+//   * only the photon sets a busy bit and only the walker that holds the slot's segment clears
+//     it, so a bit the photon has read clear stays clear until the photon itself sets it;
+//   * a walker writes only its own slot's cell word (pcell) and clears only its own bit, and the
+//     token carries the slot, so no role depends on the order in which slots are taken;
+//   * the photon remembers the slot it pushed last (P.seq bits 0-1). That slot holds the
+//     photon's newest segment, whichever finishes last: a synchronous segment's completion
+//     (LF_WAIT) watches its bit, and the final cells of an absorbed or recorded photon are its
+//     cell word once the whole busy word is 0;
+//   * an emission and a Fresnel event need a slot for their inputs and results. It is chosen
+//     when the event is queued (any free one), sent in the event code and kept in P.seq bits
+//     2-3; the photon hands out nothing while its event is queued, so the slot stays free until
+//     the photon has read the results.
+// The two-slot instantiation differs in SL only. Hand-outs that took another slot than the
+// rotation would have are counted per lane and summed at the wave's exit
+// (smcrt_scene_out_of_order_handouts). The
 // ring (multi-producer, multi-consumer, LDS) carries only tokens: owner, slot, synchronous flag.
 // Tickets are matched one to one: photon waves take them from `tail` (one reserved per
 // segment), walker lanes from `head` (one held per idle lane; head may run ahead of tail).
@@ -56,8 +74,8 @@
 //     or past it, and a walker wave ends when it holds no segment and no earlier ticket.
 // Otherwise no wave waits for another except a photon for its synchronous segment (and the
 // bucket claims of deposit.h among the walker waves, whose bound is unchanged: only walkers
-// deposit). An emission's position comes back in the start fields of the photon's next slot,
-// which must be free when the emission is queued.
+// deposit). An emission's position comes back in the start fields of a free slot of the photon;
+// with none free the emission is queued on a later trip.
 //
 // In-voxel segments (SMCRT_WS_INVOXEL; by default on in the plain instantiation and off in the XF
 // one, see the template parameter IV). Sphere tracing shortens its steps
@@ -84,9 +102,9 @@
 //   * the batched P7 block is only the terminal interactions (tflag or fault, the
 //     MAX_INTERACTIONS stop) and completion; an interaction that draws, a tauint2 entry and an
 //     emission always go to the event waves;
-//   * a fetched photon whose slot P.seq is still busy (a deferred segment of the lane's previous
-//     photon is still being walked) stays in ST_EMIT and queues its emission on a later trip.
-//     The slot is freed by the walker that holds its segment, and no walker waits for a photon
+//   * a fetched photon all of whose slots are still busy (deferred segments of the lane's previous
+//     photon are still being walked) stays in ST_EMIT and queues its emission on a later trip.
+//     A slot is freed by the walker that holds its segment, and no walker waits for a photon
 //     (a walker waits only for bucket claims among walkers), so this wait closes no cycle: it is
 //     the wait of a hand-out for its slot. It counts among the states in which "every photon
 //     of the wave waits", so the wave yields and the watchdog covers it;
@@ -119,17 +137,42 @@ namespace smcrt {
 #endif
 // the photon hands a segment's start cell to its walker in the slot's cell word (1) instead of
 // the walker recomputing it from the start (0); the same cell_of on the same start either way
-// the plain instantiation reads the deferral box from KParams too (1) or keeps it in VGPRs (0)
-#ifndef SMCRT_WS_KBOUNDS_PLAIN
-#define SMCRT_WS_KBOUNDS_PLAIN 0
-#endif
-// the photon waves' EVAL takes top-level spheres and boxes two at a time (1; transport.h
-// eval_sdfs PAIRS) or one by one (0)
-#ifndef SMCRT_WS_EVAL_PAIRS
-#define SMCRT_WS_EVAL_PAIRS 0
-#endif
 #ifndef SMCRT_WS_START_CELLS
 #define SMCRT_WS_START_CELLS 1
+#endif
+// Two forms that ws_kernel decides per instantiation (WsTraits below); -DSMCRT_WS_KBOUNDS_PLAIN=0/1
+// and -DSMCRT_WS_EVAL_PAIRS=0/1 force one form on every instantiation (tools/variants.sh):
+//   * the deferral box of an instantiation without XF: read from KParams at the hand-out (1), as
+//     the XF instantiations always do, or kept in VGPRs (0);
+//   * the photon waves' EVAL takes top-level spheres and boxes two at a time (1; transport.h
+//     eval_sdfs PAIRS) or one by one (0); the same operations either way (sdf_prim_s with the
+//     kind a constant), so the results are the same bit for bit.
+// Power-of-two grids (GM 2) have no face arrays and no in_cell test in their hand-out, so their
+// plain instantiation has the registers for both (M1, profiles/r11_photon_bound/ab.txt). The
+// other grid modes lost with either (M0 -1.4 % and -2.3 %, profiles/r08_tk/ab_tk.txt) and keep
+// the old forms, as does the XF instantiation its one-by-one EVAL.
+template <int GM, bool XF>
+struct WsTraits {
+#ifdef SMCRT_WS_KBOUNDS_PLAIN
+  static constexpr bool KBOUNDS = XF || SMCRT_WS_KBOUNDS_PLAIN != 0;
+#else
+  static constexpr bool KBOUNDS = XF || GM == 2;
+#endif
+#ifdef SMCRT_WS_EVAL_PAIRS
+  static constexpr bool EVAL_PAIRS = SMCRT_WS_EVAL_PAIRS != 0;
+#else
+  static constexpr bool EVAL_PAIRS = GM == 2 && !XF;
+#endif
+};
+// the hand-out takes any free slot of the photon (1) or the next one in rotation (0, the policy
+// before; kept for A/B builds)
+#ifndef SMCRT_WS_ANY_SLOT
+#define SMCRT_WS_ANY_SLOT 1
+#endif
+// issue priority of the photon waves (s_setprio; the event wave runs at 3, the walkers at 0);
+// 1 and 2 measured again with the photon waves the binding role: profiles/r11_photon_bound/ab.txt
+#ifndef SMCRT_WS_PHOTON_PRIO
+#define SMCRT_WS_PHOTON_PRIO 0
 #endif
 // a photon lane's pending in-voxel deposits (see "In-voxel segments"): in VGPRs (0), or in LDS (1),
 // 6 KiB per block, which moves grids of about 1024 tiles from three segment slots to two
@@ -218,6 +261,20 @@ __device__ __forceinline__ uint32_t ws_busy(S* sh, uint32_t pl) {
   return __hip_atomic_load(&sh->busy[pl], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// The slot a photon may write next, given its busy word and the slot it pushed last: the lowest
+// free one (SL: none is free). ws_next is the slot the rotation would take.
+template <uint32_t SL>
+__device__ __forceinline__ uint32_t ws_next(uint32_t last) { return last + 1u == SL ? 0u : last + 1u; }
+template <uint32_t SL>
+__device__ __forceinline__ uint32_t ws_pick(uint32_t busy, uint32_t last) {
+#if SMCRT_WS_ANY_SLOT
+  return (uint32_t)__builtin_ctz(~busy | (1u << SL));
+#else
+  const uint32_t s = ws_next<SL>(last);
+  return (busy >> s & 1u) ? SL : s;
+#endif
+}
+
 __device__ __forceinline__ uint32_t ws_load(uint32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
@@ -236,7 +293,8 @@ enum : int { WD_WITERS = 20, WD_WIDLE, WD_WBUSY, WD_WPEND, WD_PTRIPS, WD_PSLEEP,
              // s_memtime ticks per region (WST): photon waves, walker waves, event waves
              WD_TP_FETCH, WD_TP_POLL, WD_TP_EVAL, WD_TP_P34, WD_TP_HAND, WD_TP_P56, WD_TP_P7, WD_TP_P8,
              WD_TW_CLAIM, WD_TW_IDLE, WD_TW_WALK, WD_TW_FIN, WD_TE_RUN, WD_TE_IDLE,
-             WD_PEMITW,  // lanes whose emission waited for its slot (!TK), per trip
+             WD_PEMITW,  // lanes whose emission waited for a slot (!TK), per trip
+             WD_POOO,    // hand-outs into another slot than the next in rotation
              WD_N };
 static_assert(WD_N <= 64, "g_diag[64..] belongs to transport_kernel");
 #define WSDIAG(i, v) (wd[(i) - WD_WITERS] += (uint64_t)(v))
@@ -315,7 +373,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
   uint32_t w_iters = 0, w_sdf = 0, w_dep = 0, hazards = 0;
   // per-lane tallies of the frequent counters, summed over the wave at the end (the rare ones
   // go through ws_count into the wave's LDS counters)
-  uint32_t r_upd = 0, r_scat = 0, r_tau = 0, r_abs = 0, r_inv = 0;
+  uint32_t r_upd = 0, r_scat = 0, r_tau = 0, r_abs = 0, r_inv = 0, r_ooo = 0;
 #ifdef SMCRT_DIAG
   uint64_t wd[WD_N - WD_WITERS] = {};
   uint64_t tprev = __builtin_amdgcn_s_memtime();
@@ -326,6 +384,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
     const bool test_kernel = TK && (K.flags & SMCRT_FLAG_TEST_KERNEL) != 0;
     const bool records_on = (K.flags & SMCRT_FLAG_RECORD_PHOTONS) != 0 && C->records != nullptr;
     const uint32_t pl = threadIdx.x;  // photon lane (the photon waves come first)
+    if constexpr (SMCRT_WS_PHOTON_PRIO != 0) __builtin_amdgcn_s_setprio(SMCRT_WS_PHOTON_PRIO);
 #define WLU(f) (sh->lu[(f)][pl])
     // lean_margin (lean.h), per axis, corner coordinates; SMCRT_DEBUG_LEAN_MARGIN (tests only)
     // (the XF instantiation reads the box from KParams at the hand-out instead, see there)
@@ -365,7 +424,8 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
     P.pos = P.dir = v3(0.0, 0.0, 0.0);
     P.tau = P.taurun = P.d = P.minabs = 0.0;
     P.layer = P.xcell = P.ycell = P.zcell = 0;
-    P.hop = P.loopc = P.seq = 0;
+    P.hop = P.loopc = 0;
+    P.seq = WS_SLOTS - 1u;  // (the rotation would start at slot 0)
     P.rng.init(0);
     uint64_t chunk_base = 0;
     uint32_t chunk_left = 0;
@@ -437,7 +497,8 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             P.rng.cached = sh->ev_cached[pl];
           }
           if (P.st == ST_EMIT) {  // the emitted photon (its tauint2 entry follows the layer search)
-            P.pos = v3(sh->seg[P.seq][SG_OX][pl], sh->seg[P.seq][SG_OY][pl], sh->seg[P.seq][SG_OZ][pl]);
+            const uint32_t es = P.seq >> 2;  // (the free slot chosen at the enqueue)
+            P.pos = v3(sh->seg[es][SG_OX][pl], sh->seg[es][SG_OY][pl], sh->seg[es][SG_OZ][pl]);
             P.dir = v3(sh->ev_dir[0][pl], sh->ev_dir[1][pl], sh->ev_dir[2][pl]);
             P.clr(LF_TFLAG);
             P.layer = (int32_t)(code & 0xFFFFu);
@@ -466,9 +527,10 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
                 p8();
               }
             } else {  // refracted: cross with the new direction from smallStepPos, :284-303
-              X[WX_SSP * xs] = sh->seg[P.seq][SG_DX][pl];
-              X[(WX_SSP + 1) * xs] = sh->seg[P.seq][SG_DY][pl];
-              X[(WX_SSP + 2) * xs] = sh->seg[P.seq][SG_DZ][pl];
+              const uint32_t es = P.seq >> 2;  // (the free slot chosen at the enqueue)
+              X[WX_SSP * xs] = sh->seg[es][SG_DX][pl];
+              X[(WX_SSP + 1) * xs] = sh->seg[es][SG_DY][pl];
+              X[(WX_SSP + 2) * xs] = sh->seg[es][SG_DZ][pl];
               P.dir = v3(sh->ev_dir[0][pl], sh->ev_dir[1][pl], sh->ev_dir[2][pl]);
               P.layer = (int32_t)XI[WXI_NEWL * xs];
               P.st = ST_X1;
@@ -493,7 +555,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
       WSDIAG(WD_PIDLE, __popcll(__ballot(P.st == ST_IDLE)));
       WSDIAG(WD_PWAIT, __popcll(__ballot(P.has(LF_WAIT))));
       WSDIAG(WD_PEVQ, __popcll(__ballot(P.has(LF_EVQ))));
-      WSDIAG(WD_PEMITW, __popcll(__ballot(!TK && P.st == ST_EMIT && !P.has(LF_EVQ) && (ws_busy(sh, pl) & (1u << P.seq)))));
+      WSDIAG(WD_PEMITW, __popcll(__ballot(!TK && P.st == ST_EMIT && !P.has(LF_EVQ) && ws_pick<WS_SLOTS>(ws_busy(sh, pl), P.seq & 3u) == WS_SLOTS)));
 
       WST(WD_TP_POLL);
       // ---- EVAL: the SDF array at the photon's query point ------------------------------------
@@ -503,7 +565,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
       if (__ballot(have)) {
         const bool mask_le = test_kernel && P.st == ST_LAYER;
         const V3 q = (P.st == ST_H1 || P.st == ST_G0) ? P.pos + smul(P.d, P.dir) : P.pos;
-        R = eval_sdfs<false, SMCRT_WS_EVAL_PAIRS != 0>(nodes, prog, K.n_prog, q, mask_le, 0, 0);
+        R = eval_sdfs<false, WsTraits<GM, XF>::EVAL_PAIRS>(nodes, prog, K.n_prog, q, mask_le, 0, 0, !(K.lean_debug & 8u));
         const bool counted = P.st == ST_H0 || P.st == ST_H1 || P.st == ST_H3 || P.st == ST_M1 || P.st == ST_G0;
         w_sdf += __popcll(__ballot(have && counted)) * (uint32_t)K.n_top;
         WSDIAG(WD_ELANES, __popcll(__ballot(have)));
@@ -596,7 +658,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
       if (__ballot(P.has(LF_REQ))) {
         bool push = false, sync = false;
         V3 old = v3(0.0, 0.0, 0.0);
-        const uint32_t slot = P.seq;
+        uint32_t slot = WS_SLOTS;  // (a free slot of the photon, looked for once the segment needs one)
         bool inv = false;
         int32_t ci = -1, cj = -1, ck = -1;
         if constexpr (IV) {
@@ -631,7 +693,8 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
           P.clr(LF_REQ | LF_MOVE_FWD | LF_MOVE_BACK);
           P.xcell = ci; P.ycell = cj; P.zcell = ck;
           P.set(LF_CELLS);
-        } else if (P.has(LF_REQ) && !(ws_busy(sh, pl) & (1u << slot))) {  // (else: retry next trip)
+        } else if (P.has(LF_REQ) &&
+                   (slot = ws_pick<WS_SLOTS>(ws_busy(sh, pl), P.seq & 3u)) < WS_SLOTS) {  // (else: retry next trip)
           ++r_upd;
           if constexpr (!IV) {  // (the start and its cell, once the slot is free)
             old = v3(P.pos.x + K.xmax, P.pos.y + K.ymax, P.pos.z + K.zmax);
@@ -653,7 +716,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             // spilled to scratch and was reloaded here): M3 181.0/181.6 vs 172.9/173.1 M photons/s.
             // The other one keeps it in VGPRs, where its register allocation is faster: M1 with
             // KParams 252.3 vs 257.5 M (profiles/r06_s7/ab_kparams_bounds.txt).
-            constexpr bool KB = XF || SMCRT_WS_KBOUNDS_PLAIN;
+            constexpr bool KB = WsTraits<GM, XF>::KBOUNDS;
             const double mx = KB ? K.lean_lo[0] : mx0, my = KB ? K.lean_lo[1] : my0, mz = KB ? K.lean_lo[2] : mz0;
             const double ex = KB ? K.lean_hi[0] : ex0, ey = KB ? K.lean_hi[1] : ey0, ez = KB ? K.lean_hi[2] : ez0;
             const bool inside = old.x >= mx && old.x <= ex && old.y >= my && old.y <= ey && old.z >= mz &&
@@ -678,6 +741,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
         }
         const uint64_t pm = __ballot(push);
         WSDIAG(WD_PUSH, __popcll(pm));
+        WSDIAG(WD_POOO, __popcll(__ballot(push && slot != ws_next<WS_SLOTS>(P.seq & 3u))));
         WSDIAG(WD_PBLOCKED, __popcll(__ballot(P.has(LF_REQ))));
         if (pm) {
           const int first = __builtin_ctzll(pm);
@@ -705,7 +769,8 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             }
             __hip_atomic_store(&sh->meta[ix], pl | (slot << 9) | (sync ? (1u << 11) : 0u) | ws_tick(t),
                                __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            P.seq = P.seq + 1 == WS_SLOTS ? 0u : P.seq + 1;
+            if (slot != ws_next<WS_SLOTS>(P.seq & 3u)) ++r_ooo;  // (not the slot the rotation would take)
+            P.seq = slot;  // the slot pushed last (no event of the photon is queued here)
             P.clr(LF_CELLS);
             if (sync) P.set(LF_WAIT);
           }
@@ -714,8 +779,8 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
 
       WST(WD_TP_HAND);
       // ---- P5: a synchronous segment finished; after a segment: next program point ---------
-      if (P.has(LF_WAIT) && !(ws_busy(sh, pl) & (1u << ((P.seq + WS_SLOTS - 1) % WS_SLOTS)))) {
-        const unsigned long long w = sh->pcell[pl][(P.seq + WS_SLOTS - 1) % WS_SLOTS];
+      if (P.has(LF_WAIT) && !(ws_busy(sh, pl) & (1u << (P.seq & 3u)))) {
+        const unsigned long long w = sh->pcell[pl][P.seq & 3u];
         P.xcell = lean_cell(w, 0); P.ycell = lean_cell(w, 1); P.zcell = lean_cell(w, 2);
         P.set(LF_CELLS);
         if (w & LEAN_TFLAG) P.set(LF_TFLAG);
@@ -759,7 +824,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
       }
       // the final cells of the photon's deferred segments, once they are all done
       if (!P.has(LF_CELLS) && (P.st == ST_ABSORB || (records_on && P.st == ST_DONE)) && ws_busy(sh, pl) == 0) {
-        const unsigned long long w = sh->pcell[pl][(P.seq + WS_SLOTS - 1) % WS_SLOTS];
+        const unsigned long long w = sh->pcell[pl][P.seq & 3u];  // (the segment handed out last)
         P.xcell = lean_cell(w, 0); P.ycell = lean_cell(w, 1); P.zcell = lean_cell(w, 2);
         P.set(LF_CELLS);
       }
@@ -778,11 +843,17 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
         // waves; a Fresnel event always goes to the event waves. Keeping them in the photon waves
         // for detector scenes too measured M5 34.3-34.9 vs 30.8-30.9 M photons/s, still short of
         // transport_kernel's 42.7-43.5, profiles/r05_ws/ab_m5_inline.txt)
+        // (an emission and a Fresnel event need a free slot of the photon, which carries their
+        // inputs and results: chosen here, kept in P.seq bits 2-3 and sent in the event code; it
+        // stays free until the result is read, since the photon pushes nothing meanwhile)
+        uint32_t es = 0;
+        const bool need_slot = (!test_kernel && P.st == ST_EMIT) || (XF && P.st == ST_F0);
+        if (need_slot && free_ && !P.has(LF_EVQ)) es = ws_pick<WS_SLOTS>(ws_busy(sh, pl), P.seq & 3u);
         bool qev = free_ && !P.has(LF_EVQ) &&
                    ((!test_kernel && ((P.st == ST_INTERACT && !(P.f & (LF_TFLAG | LF_FAULT)) &&
                                      WLU(LL_INTER) + 1u <= (uint32_t)MAX_INTERACTIONS) ||
-                                    P.st == ST_T2 || (P.st == ST_EMIT && !(ws_busy(sh, pl) & (1u << P.seq))))) ||
-                    (XF && P.st == ST_F0 && !(ws_busy(sh, pl) & (1u << P.seq))));
+                                    P.st == ST_T2 || (P.st == ST_EMIT && es < WS_SLOTS))) ||
+                    (XF && P.st == ST_F0 && es < WS_SLOTS));
         if (drop_event && qev) {  // (debug knob: a missed enqueue; the photon waits for nothing)
           drop_event = qev = false;
           __hip_atomic_store(&sh->ev_code[pl], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -810,8 +881,8 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
               sh->ev_draws[pl] = P.rng.draws;
             }
             if (XF && P.st == ST_F0) {  // reflect_refract's inputs: pos and step in the free slot, the new layer
-              sh->seg[P.seq][SG_OX][pl] = P.pos.x; sh->seg[P.seq][SG_OY][pl] = P.pos.y;
-              sh->seg[P.seq][SG_OZ][pl] = P.pos.z; sh->seg[P.seq][SG_LEN][pl] = P.d;
+              sh->seg[es][SG_OX][pl] = P.pos.x; sh->seg[es][SG_OY][pl] = P.pos.y;
+              sh->seg[es][SG_OZ][pl] = P.pos.z; sh->seg[es][SG_LEN][pl] = P.d;
               sh->ev_tau[pl] = (double)XI[WXI_NEWL * xs];
             }
             if (P.st == ST_EMIT) {  // kernelsMod.f90:1937-1945: a fresh packet
@@ -822,7 +893,8 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             sh->ev_code[pl] = (uint32_t)P.layer |
                               ((P.st == ST_INTERACT ? WS_EV_INTERACT
                                 : (P.st == ST_T2 ? WS_EV_TAU : (P.st == ST_EMIT ? WS_EV_EMIT : WS_EV_FRESNEL))) << 16) |
-                              (P.seq << 19);
+                              (es << 19);
+            P.seq = (P.seq & 3u) | (es << 2);
             __hip_atomic_store(&sh->evq[ix], pl | ws_tick(t), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             P.set(LF_EVQ);
           }
@@ -1270,7 +1342,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
     unsigned long long* const counters = C->counters;
     const uint32_t hz = wave_sum_u32(hazards);
     const uint32_t n_upd = wave_sum_u32(r_upd), n_scat = wave_sum_u32(r_scat), n_tau = wave_sum_u32(r_tau),
-                   n_abs = wave_sum_u32(r_abs), n_inv = wave_sum_u32(r_inv);
+                   n_abs = wave_sum_u32(r_abs), n_inv = wave_sum_u32(r_inv), n_ooo = wave_sum_u32(r_ooo);
     if (lane_id == 0) {
       if (hz) {  // reported: smcrt_kernel_times.lean_hazards, and SMCRT_CTR_FAULTS
         atomicAdd(C->dep_ctl + 5, hz);
@@ -1278,6 +1350,7 @@ __global__ __launch_bounds__(WS_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
       }
       if (C->dep_ctl && n_upd) atomicAdd(C->dep_ctl + 6, n_upd);  // segments
       if (n_inv) atomicAdd(C->invoxel_segs, (unsigned long long)n_inv);  // (each also one deposit)
+      if (n_ooo) atomicAdd(C->ooo_handouts, (unsigned long long)n_ooo);
       if (counters) {
         const uint32_t* c = sh->wctr[wv];
         const uint32_t v[SMCRT_NCOUNTERS] = {c[LC_PHOTONS], c[LC_RETRIES], n_scat,        n_abs,          w_sdf,

@@ -512,6 +512,17 @@ class Engine:
         return n.value
 
 
+    def out_of_order_handouts(self) -> int:
+        """Segments of the scene's finished lean launches that went into a slot other than the next
+        one in rotation (smcrt_scene_out_of_order_handouts), a running total; a schedule
+        statistic that varies from run to run."""
+        fn = load_library().smcrt_scene_out_of_order_handouts
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        n = C.c_int64()
+        _check(fn(self._h, C.byref(n)))
+        return n.value
+
+
 def pack_layout(grid, n_det_bins: int, fields: int) -> abi.PackLayout:
     lay = abi.PackLayout()
     lay.n_voxels, lay.n_det_bins, lay.fields = grid.nx * grid.ny * grid.nz, int(n_det_bins), int(fields)
